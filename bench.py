@@ -12,10 +12,13 @@ One step = `launches_per_step` passes of the path over the batch.  The count is 
 timed region lasts >= --min-seconds whatever --steps is (a 256-tick launch is ~1 ms); the K steps are timed exactly as
 the contract says (barrier + device sync on both sides, max over ranks).
 
-The other BASELINE configs (cfg2 convert+scale, cfg3 4 x BGRA composite, cfg5 4K 8-layer + Lanczos, the reference's own 4:2:0 mixer canvas, the
-encoder-side frame, the planar / grid / logo variants of the pipeline) are timed the same way right after; `--full` adds the legs that are not
-kernel throughput (cfg2 and the whole chain end to end over PCIe, one tick at a time, thread scaling, route regret, clock and power of every
-workload).
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs and nothing else: it builds the headline batch, warms
+up, times the K steps, writes the last step's canvases when `--dump-outputs DIR` is given, and prints the line.  Everything else is
+behind `--full`: the oracle check of the timed canvases, the CPU baseline, the other BASELINE configs (cfg2 convert+scale, cfg3 4 x BGRA
+composite, cfg5 4K 8-layer + Lanczos, the reference's own 4:2:0 mixer canvas, the encoder-side frame, the planar / grid / logo variants of
+the pipeline, timed the same way right after the headline), the counted HBM traffic (rocprofv3 child passes), and the legs that are not
+kernel throughput (cfg2 and the whole chain end to end over PCIe, one tick at a time, thread scaling, route regret, clock and power of
+every workload).
 
 Multi-GPU: weak scaling, one process per GPU, no collective on the data path (stream s -> device s mod N).  When started without a launcher
 (`python bench.py --gpus N`, no WORLD_SIZE in the environment) the script spawns its N ranks itself; under torch.distributed.run it reads
@@ -25,8 +28,9 @@ Output (rank 0): the LAST stdout line is ONE compact JSON object (< 4 KB, compac
   value        = target pixels written per second, whole job, inputs resident in HBM
   config       = the workload, launches and frames per step, kernel, oracle verdict, per-GPU rates, every workload's [fraction of 8 TB/s, ms per launch]
   roofline     = algorithmic bytes per launch / mean launch duration (HIP events on the context's stream) against the 8 TB/s HBM peak, the counted
-                 HBM traffic of the same kernel (two rocprofv3 --pmc child passes), the limiter the round's probes name, clock and power
-  cpu_baseline = the oracle (CPU restatement of the same kernels, "port") timed on the host cores of this box on a bounded sample (N=1 only)
+                 HBM traffic of the same kernel (--full: two rocprofv3 --pmc child passes; otherwise the committed figure, if any), the limiter
+                 the round's probes name, clock and power (--full)
+  cpu_baseline = (--full) the oracle (CPU restatement of the same kernels, "port") timed on the host cores on a bounded sample (N=1 only)
 and everything else — every workload's full record, the legs, build flags, prose — is written to bench_detail.json (--detail-json).
 """
 import argparse
@@ -117,7 +121,7 @@ def parse_args(argv=None):
                     help="the workload `value` / `roofline` are reported on")
     ap.add_argument("--also", default=None,
                     help="comma-separated workloads timed after the headline and reported under \"workloads\" "
-                         "(default: the BASELINE set when --workload is the default, none otherwise); 'none' for none")
+                         "(default: the BASELINE set under --full when --workload is the default, none otherwise); 'none' for none")
     ap.add_argument("--group", type=int, default=0,
                     help="ticks per launch GROUP of workloads with a second stage (cfg5: composite, then Lanczos): the batch is issued as frames / G "
                          "pairs of launches (composite G ticks, resize G canvases) so that the second stage reads canvases the first one just wrote "
@@ -129,9 +133,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--full", action="store_true",
-                    help="every leg on top of the default command (headline + the default workloads + live PMC + CPU sample): the upload-inclusive "
+                    help="everything beyond the headline's timing (a plain run times the headline alone): the oracle check of every timed "
+                         "workload, the CPU sample, the default workloads (when --also is not given), live PMC, and every leg: the upload-inclusive "
                          "and end-to-end legs, the one-tick-at-a-time legs, thread scaling, route regret, clock / power of every workload.  "
                          "They go to bench_detail.json; the last stdout line stays the compact one either way")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (float32, < 64 MB in all): "
+                         "the whole canvases of the first and last tick where they fit, and a fixed, seeded sample of every tick's canvas")
     ap.add_argument("--detail-json", default=None,
                     help="where rank 0 writes the full report (every workload's record, the legs, build flags, prose): default bench_detail.json "
                          "next to this script; 'none' to write nothing")
@@ -141,9 +149,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-per-tick", action="store_true", help="skip the one-tick-at-a-time legs (pipeline_per_tick, pipeline_reference_sequence)")
     ap.add_argument("--per-tick", action="store_true", help="run the one-tick-at-a-time legs even with --also none")
     ap.add_argument("--route-regret", action="store_true", help="run the route-regret leg even with --also none (for the headline workload)")
-    ap.add_argument("--no-route-regret", action="store_true", help="skip the route-regret leg of the default run")
+    ap.add_argument("--no-route-regret", action="store_true", help="skip the route-regret leg of --full")
     ap.add_argument("--power-probe", action="store_true", help="run the clock / power leg even with --also none (for the headline workload)")
-    ap.add_argument("--no-power-probe", action="store_true", help="skip the clock / power leg of the default run")
+    ap.add_argument("--no-power-probe", action="store_true", help="skip the clock / power leg of --full")
     ap.add_argument("--alias", default="none", choices=("none", "src", "dst", "both"),
                     help="DIAGNOSTIC (single-layer YUV workloads): every tick reads frame 0's source and/or writes frame 0's "
                          "canvas, so that side of the traffic stays in cache; the line is marked and is not a benchmark result")
@@ -168,7 +176,10 @@ def parse_args(argv=None):
     ap.add_argument("--pmc-json", default=None,
                     help="a profiles/pmc_*.json produced by profiles/run_profile.sh for THIS command: its HBM bytes per launch "
                          "are copied into roofline.traffic with roofline.traffic_source naming the file")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.stub_device or args.with_upload):
+        ap.error("--dump-outputs: the batch mode on a device only (a stub device computes nothing; --with-upload is not the headline mode)")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -565,6 +576,51 @@ def verify_frame(sv, ctx, wl, w, frame=0):
     return True
 
 
+DUMP_FULL_BYTES = 40 << 20       # --dump-outputs: whole planes (float32) of the first and the last tick, as far as they fit
+DUMP_SAMPLE_BYTES = 16 << 20     # --dump-outputs: the seeded sample of every tick's planes
+
+
+def dump_outputs(sv, ctx, wl, w, out_dir):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files under out_dir (< 64 MB in all).  Every launch clears and
+    recomposes each tick's canvas, so after the timed region the canvases (the Lanczos outputs of two-stage workloads) hold the last step's
+    result.  Written (pitch padding cut off, a plane's elements in row-major order):
+      tick<f>_plane<p>.npy   plane p of tick f, whole, for the first and the last tick while they fit in DUMP_FULL_BYTES
+      sample_plane<p>.npy    shape (ticks, k): k elements of every tick's plane p at positions drawn from a fixed seed (DUMP_SAMPLE_BYTES)
+    Returns the names written."""
+    import util
+    if w["lanczos"]:
+        pics, fmt, (cw, ch) = [small for small, _ in w["lanczos"]], "bgra", wl["lanczos"]
+    else:
+        pics, fmt, (cw, ch) = w["canvases"], w["verify"]["target"], (wl["dw"], wl["dh"])
+    shapes = [p.shape for p in util.alloc_image(fmt, cw, ch)]
+    sizes = [int(np.prod(s)) for s in shapes]
+    n = len(pics)
+    whole, budget = [], DUMP_FULL_BYTES
+    for f in sorted({0, n - 1}):
+        if 4 * sum(sizes) <= budget:
+            whole.append(f)
+            budget -= 4 * sum(sizes)
+    rng = np.random.default_rng(0x5EED)
+    k = [min(s, DUMP_SAMPLE_BYTES // 4 // len(sizes) // n) for s in sizes]
+    idx = [np.sort(rng.integers(0, s, (n, kk)), axis=1) for s, kk in zip(sizes, k)]
+    samples = [np.empty((n, kk), dtype=np.float32) for kk in k]
+    out_dir.mkdir(parents=True, exist_ok=True)
+    names = []
+    for f, pic in enumerate(pics):
+        got = sv.downloadComputePicture(ctx, pic, retainGpuBuffer=True).imageBuffer().buffers
+        for p, (g, shape) in enumerate(zip(got, shapes)):
+            comps = 1 if len(shape) == 2 else shape[2]
+            plane = np.ascontiguousarray(g[: shape[0], : shape[1] * comps]).reshape(-1)
+            samples[p][f] = plane[idx[p][f]]
+            if f in whole:
+                names.append(f"tick{f:04d}_plane{p}")
+                np.save(out_dir / f"{names[-1]}.npy", plane.reshape(shape).astype(np.float32))
+    for p, s in enumerate(samples):
+        names.append(f"sample_plane{p}")
+        np.save(out_dir / f"{names[-1]}.npy", s)
+    return names
+
+
 def cpu_baseline(wl, w, budget_s):
     """The oracle on this box's host cores, same kernels/uniforms, bounded sample.
     Stream-parallel like the GPU path: every worker thread composites whole ticks on its
@@ -767,18 +823,20 @@ def measure(name, args, sv, cv, lib, ctx, tm, rank, n_gpus, headline):
         launch()
     tm.sync()
     verified = None
-    if not args.no_verify and rank == 0 and w["verify"] is not None and (not headline or args.alias == "none"):
+    if args.full and not args.no_verify and rank == 0 and w["verify"] is not None and (not headline or args.alias == "none"):
         verified = verify_frame(sv, ctx, wl, w, 0) and verify_frame(sv, ctx, wl, w, frames - 1)
     per_step = tm.calibrate(launch, args.steps, args.min_seconds if headline else args.min_seconds_other, args.launches_per_step)
     elapsed, local, launch_ms = tm.run(launch, args.steps, per_step)
     rep = report_of(name, wl, args, tm, n_gpus, frames, per_step, elapsed, local, launch_ms, w["kernel"], verified)
+    if headline and rank == 0 and args.dump_outputs:
+        rep["dumped_outputs"] = dump_outputs(sv, ctx, wl, w, Path(args.dump_outputs))
     if lzs is not None:
         rep["kernel_launches_per_batch"] = 2 * len(w["batches"])
         rep["ticks_per_group"] = w["batches"][0][2]
     elif w.get("launches_per_batch", 1) > 1:
         rep["kernel_launches_per_batch"] = w["launches_per_batch"]       # (a split batch: the videos, then the rest; `launch_ms` covers both)
     cpu = None
-    if headline and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and w["verify"] is not None:
+    if args.full and headline and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and w["verify"] is not None:
         cpu = cpu_baseline(wl, w, args.cpu_seconds)
     free_workload(w)
     return rep, cpu
@@ -1589,7 +1647,8 @@ def run_rank(args, rank, local, world, dist):
 
     head, cpu = do(args.workload, True)
     if args.also is None:
-        others = [n for n in DEFAULT_SET if n != args.workload] if args.workload == HEADLINE else []
+        # (the default set: --full only; a plain run times the headline alone)
+        others = [n for n in DEFAULT_SET if n != args.workload] if (args.full and args.workload == HEADLINE) else []
     else:
         others = [n for n in args.also.split(",") if n and n != "none"]
     reports = {args.workload: head}
@@ -1609,9 +1668,9 @@ def run_rank(args, rank, local, world, dist):
     if ((args.full and others) or args.route_regret) and real and not args.no_route_regret and n_gpus == 1:
         regret = run_route_regret(args, sv, cv, lib, ctx, [n for n in ([args.workload] + others) if n in WORKLOADS])
     power = None
-    if real and not args.no_power_probe and n_gpus == 1 and (others or args.power_probe):
-        # the default command samples the headline's clock / power only (1.5 s); --full every workload's
-        probed = [n for n in ([args.workload] + (others if (args.full or args.power_probe) else [])) if n in WORKLOADS]
+    if real and not args.no_power_probe and n_gpus == 1 and ((args.full and others) or args.power_probe):
+        # every timed workload's clock / power (--full, or --power-probe)
+        probed = [n for n in [args.workload] + others if n in WORKLOADS]
         power = run_power_probe(args, sv, cv, lib, ctx, probed, args.device if args.device is not None else 0)
 
     if rank == 0:
@@ -1638,7 +1697,7 @@ def run_rank(args, rank, local, world, dist):
 #               profiles/r05_notes.md 10.4; mixer_y420p: section 4 + r06_notes.md — 128 VALU per overlay row, LDS pipe idle, below the cap)
 #   power_cap   at the socket's 1400 W with the shader clock pulled >= 5 % below its 2.4 GHz maximum (r05_notes.md section 10)
 #   latency     below the cap at full clock, staging alone 1.2-1.7x its bytes' copy time (r05_notes.md 10.5)
-# A live clock / power sample (the headline in the default run, every workload under --full) overrides the table where it shows the cap.
+# A live clock / power sample (every timed workload, under --full or --power-probe) overrides the table where it shows the cap.
 LIMITER_TABLE = {"pipeline": "valu_issue", "pipeline_y420p": "valu_issue", "pipeline_logo": "valu_issue", "cfg2": "valu_issue", "cfg2_y420p": "valu_issue",
                  "cfg3": "power_cap", "cfg5": "power_cap", "mixer_y420p": "valu_issue", "mixer_nv12": "valu_issue", "y420p_main": "valu_issue",
                  "encode_nv12": "valu_issue", "pipeline_grid": "latency", "mixed": "latency"}
@@ -1680,8 +1739,8 @@ def build_detail(args, dist, n_gpus, head, cpu, reports, regret, power, build_fl
     # this script after the timed regions; where rocprofv3 is missing, the committed measurement of the same workload — and the field says which
     pmc_path = Path(args.pmc_json) if args.pmc_json else ROOT / "profiles" / "pmc_latest.json"
     live_err = None
-    # (the default run only — what the driver times; `--also …` runs are the builder's A/Bs and profiling passes)
-    if n_gpus == 1 and args.also is None and not args.no_live_pmc and not args.stub_device and args.alias == "none" and not args.pmc_json:
+    # (--full with the default set only; `--also …` runs are the builder's A/Bs and profiling passes)
+    if args.full and n_gpus == 1 and args.also is None and not args.no_live_pmc and not args.stub_device and args.alias == "none" and not args.pmc_json:
         kname = head["kernel"].split("<")[0]
         t, live_err = live_traffic(args.workload, head["frames_per_launch_per_gpu"], kname, args.device if args.device is not None else 0)
         if t is not None:

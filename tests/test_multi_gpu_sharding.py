@@ -156,7 +156,7 @@ def test_two_ranks_on_one_device_end_to_end():
     its own context, frames and canvases on device 0; every rank's output is verified against the oracle by rank 0's twin
     logic (verified_vs_oracle) and the line reports both ranks."""
     d = _run_bench(["--gpus", "2", "--device", "0", "--steps", "3", "--warmup", "1", "--min-seconds", "0.2", "--frames", "32",
-                    "--also", "none", "--no-cpu-baseline"])
+                    "--also", "none", "--no-cpu-baseline", "--full"])
     assert d["n_gpus"] == 2 and len(d["config"]["per_gpu_gpix"]) == 2
     assert d["config"]["verified_vs_oracle"] is True
     assert d["config"]["kernel"] == "tick_bgra_stream"       # (32 four-layer 720p ticks per rank: a launch that fills the chip)
@@ -169,7 +169,7 @@ def test_two_host_threads_in_one_process_on_one_device():
     """`--gpus 2 --device 0 --threads`: two contexts of ONE process (each chv_context_create makes its own stream and descriptor rings) driven
     from two host threads — every thread's canvases verified against the oracle, both reported"""
     d = _run_bench(["--gpus", "2", "--device", "0", "--threads", "--steps", "3", "--warmup", "1", "--min-seconds", "0.2", "--frames", "32",
-                    "--no-cpu-baseline"])
+                    "--no-cpu-baseline", "--full"])
     assert d["n_gpus"] == 2 and len(d["config"]["per_gpu_gpix"]) == 2
     assert d["config"]["parallelism"].startswith("ONE process, 2 host threads")
     assert d["config"]["verified_vs_oracle"] is True and d["config"]["kernel"] == "tick_bgra_stream"
@@ -192,13 +192,13 @@ LIMITERS = {"valu_issue", "power_cap", "latency"}
 
 
 def test_the_last_stdout_line_of_the_default_command_is_compact():
-    """The driver's command shape without a GPU (--stub-device): the last stdout line parses, is under 4 KB, carries the contract's keys, the
-    roofline object with the limiter the probes name, and every default workload's [fraction, ms]; the tables live in bench_detail.json."""
-    d, full = _run_bench(["--stub-device", "--steps", "2", "--warmup", "1", "--min-seconds", "0.1", "--min-seconds-other", "0.02"], detail=True)
+    """The driver's command shape with --full without a GPU (--stub-device): the last stdout line parses, is under 4 KB, carries the contract's
+    keys, the roofline object with the limiter the probes name, and every default workload's [fraction, ms]; the tables live in bench_detail.json."""
+    d, full = _run_bench(["--stub-device", "--full", "--steps", "2", "--warmup", "1", "--min-seconds", "0.1", "--min-seconds-other", "0.02"], detail=True)
     cfg, r = d["config"], d["roofline"]
     assert set(cfg["workload_fracs"]) == DEFAULT_NAMES and all(len(v) == 2 and all(isinstance(x, float) for x in v) for v in cfg["workload_fracs"].values())
     assert set(cfg["workload_limiters"]) == DEFAULT_NAMES and set(cfg["workload_limiters"].values()) <= LIMITERS
-    assert cfg["full"] is False and len(cfg["per_gpu_gpix"]) == len(cfg["per_gpu_launch_ms"]) == 1
+    assert cfg["full"] is True and len(cfg["per_gpu_gpix"]) == len(cfg["per_gpu_launch_ms"]) == 1
     for k in ("bound", "limiter", "achieved", "peak", "unit", "frac", "traffic", "traffic_ratio", "kernel", "launch_ms", "issue_model_ms", "algorithmic_bytes_per_launch"):
         assert k in r, k
     assert r["bound"] == "hbm" and r["limiter"] == "valu_issue" and r["peak"] == 8000.0 and r["unit"] == "GB/s"
@@ -208,11 +208,57 @@ def test_the_last_stdout_line_of_the_default_command_is_compact():
     assert all("roofline" in v and v["roofline"]["limiter"] in LIMITERS for v in full["workloads"].values())
 
 
+def test_a_plain_run_times_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` (here on a stub device): the headline batch and nothing else — no other workload, no CPU
+    sample, no leg; K timed steps, and ms_per_step is what one of them took."""
+    d, full = _run_bench(["--stub-device", "--gpus", "1", "--steps", "3", "--warmup", "1", "--min-seconds", "0.1"], detail=True)
+    cfg = d["config"]
+    assert cfg["full"] is False and set(full["workloads"]) == {"pipeline"} and set(cfg["workload_fracs"]) == {"pipeline"}
+    assert "cpu_baseline" not in d and full["config"]["legs"] == {} and full["config"]["route_regret"] is None
+    assert d["steps"] == 3 and d["warmup"] == 1
+    assert d["ms_per_step"] == pytest.approx(full["config"]["timed_seconds"] * 1e3 / 3, rel=1e-3)
+
+
+def test_dump_outputs_is_refused_where_nothing_is_computed():
+    import subprocess
+    for mode in (["--stub-device"], ["--with-upload"]):
+        p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--dump-outputs", "never_written", "--steps", "1"] + mode,
+                           capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "--dump-outputs" in p.stderr, p.stderr[-500:]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_what_the_last_step_computed(tmp_path):
+    """--dump-outputs DIR after a plain run: float32 .npy files under 64 MB in all; the whole canvases of the first and the last tick are
+    the oracle's, and the seeded sample has a row for every tick."""
+    import numpy as np
+    import util
+    from oracle import oracle as O
+    out = tmp_path / "out"
+    d = _run_bench(["--steps", "2", "--warmup", "1", "--min-seconds", "0.1", "--frames", "8", "--dump-outputs", str(out)])
+    assert d["steps"] == 2 and d["config"]["full"] is False
+    files = sorted(out.glob("*.npy"))
+    assert {f.name for f in files} == {"tick0000_plane0.npy", "tick0007_plane0.npy", "sample_plane0.npy"}
+    assert sum(f.stat().st_size for f in files) < 64 << 20
+    srcs = [util.alloc_image("nv12", 1920, 1080, seed=0x5EED0000 + 32 + i) for i in range(4)]       # the headline's sources on rank 0
+    for f in (0, 7):
+        exp = util.alloc_image("bgra", 1280, 720)
+        assert O.run_kernel("img_clear_bgra", exp) == 0
+        for l, op in enumerate((1.0, 0.75, 0.5, 0.25)):
+            u = util.full_canvas_uniforms((1280, 720), (1920, 1080), opacity=op)
+            assert O.run_kernel("img_nv12_bgra", exp, srcs[(f + l) % 4], u, threads=8) == 0
+        got = np.load(out / f"tick{f:04d}_plane0.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, exp[0].astype(np.float32)), f"tick {f}"
+    s = np.load(out / "sample_plane0.npy")
+    assert s.dtype == np.float32 and s.shape[0] == 8 and s.shape[1] > 1000
+    assert np.isin(s[0], np.load(out / "tick0000_plane0.npy")).all() and np.isin(s[7], np.load(out / "tick0007_plane0.npy")).all()
+
+
 def test_the_compact_line_at_eight_devices_keeps_its_per_gpu_arrays():
     """what a SCALE record will carry: --gpus 8 (threads on stub devices here) -> eight per-GPU rates and launch times in a line still < 4 KB"""
     d = _run_bench(["--gpus", "8", "--threads", "--stub-device", "--steps", "2", "--warmup", "1", "--min-seconds", "0.1"])
     assert d["n_gpus"] == 8 and len(d["config"]["per_gpu_gpix"]) == len(d["config"]["per_gpu_launch_ms"]) == 8
-    d = _run_bench(["--gpus", "2", "--device", "0", "--stub-device", "--steps", "2", "--warmup", "1", "--min-seconds", "0.1", "--min-seconds-other", "0.02"])
+    d = _run_bench(["--gpus", "2", "--device", "0", "--stub-device", "--full", "--steps", "2", "--warmup", "1", "--min-seconds", "0.1", "--min-seconds-other", "0.02"])
     assert d["n_gpus"] == 2 and len(d["config"]["per_gpu_gpix"]) == len(d["config"]["per_gpu_launch_ms"]) == 2
     assert set(d["config"]["workload_fracs"]) == DEFAULT_NAMES
 
@@ -235,16 +281,17 @@ def test_the_compact_line_never_carries_nan_and_sheds_optional_keys_first():
 
 @pytest.mark.gpu
 def test_default_run_measures_its_hbm_traffic():
-    """The driver's command shape (no --also, no --full): every workload of the default set timed and verified, roofline.traffic measured in
-    the run itself by two rocprofv3 --pmc child passes (or, where rocprofv3 is missing, the committed figure — and the line says which), the
-    headline's clock and power sampled; the last stdout line compact (check_compact_line), everything else in bench_detail.json."""
+    """--full without its legs (no --also): every workload of the default set timed and verified, roofline.traffic measured in the run itself
+    by two rocprofv3 --pmc child passes (or, where rocprofv3 is missing, the committed figure — and the line says which), the headline's clock
+    and power sampled; the last stdout line compact (check_compact_line), everything else in bench_detail.json."""
     import shutil
-    d, full = _run_bench(["--steps", "2", "--warmup", "1", "--min-seconds", "0.1", "--min-seconds-other", "0.05", "--cpu-seconds", "1.5"], detail=True)
+    d, full = _run_bench(["--full", "--no-upload-leg", "--no-per-tick", "--no-route-regret", "--steps", "2", "--warmup", "1", "--min-seconds", "0.1",
+                          "--min-seconds-other", "0.05", "--cpu-seconds", "1.5"], detail=True)
     assert set(full["workloads"]) - {"power_probe"} == DEFAULT_NAMES                  # no legs in the default command
     assert all(v["verified_vs_oracle"] is True for k, v in full["workloads"].items() if k in DEFAULT_NAMES)
     assert full["config"]["build_flags"].startswith("arch=gfx950;") and "abl=0" in full["config"]["build_flags"]
     cfg = d["config"]
-    assert cfg["verified_vs_oracle"] is True and cfg["kernel"] == "tick_bgra_stream" and cfg["full"] is False
+    assert cfg["verified_vs_oracle"] is True and cfg["kernel"] == "tick_bgra_stream" and cfg["full"] is True
     assert set(cfg["workload_fracs"]) == DEFAULT_NAMES and all(0 < f[0] < 1 and f[1] > 0 for f in cfg["workload_fracs"].values())
     assert set(cfg["workload_limiters"]) == DEFAULT_NAMES and set(cfg["workload_limiters"].values()) <= LIMITERS
     r = d["roofline"]

@@ -59,11 +59,12 @@ def test_oracle_reproduces_golden_vectors(gold):
             assert np.array_equal(g, e), key
 
 
-def test_oracle_equals_compiled_reference_kernels():
-    """Kernel-body arithmetic of the restatement == the reference's OpenCL-C source compiled for
-    x86-64 (a cross-check, not a reference build: the image builtins are ours, oracle/clref/cl_shim.c)."""
-    if O.clref() is None:
-        pytest.skip("oracle/_ref/libclref.so not built (needs /root/reference)")
+CLREF_GOLD = Path(__file__).resolve().parent / "golden" / "clref_vectors.npz"
+
+
+def clref_layer_cases():
+    """(key, kernel, source, canvas before, uniforms) of the cross-check below; tests/golden/gen_clref_golden.py records the compiled
+    reference kernels' canvases of the same cases"""
     rng_geo = [dict(rect=(3, 1, 50, 30), rotation=0.9, opacity=0.45, fill=(0.3, 0.9, 0.2, 0.65), border=(4, 0, 1, 6)),
                dict(rect=(-30, -10, 140, 70), opacity=1.0, tex=(0.3, 0.4, 0.3, 0.2)),
                dict(rect=(40, 20, 10, 8), opacity=0.2, fill=(1, 1, 1, 1), border=(30, 15, 10, 5))]
@@ -73,11 +74,27 @@ def test_oracle_equals_compiled_reference_kernels():
             u = util.make_uniforms((64, 36), in_size=(48, 28), **geo)
             src = util.alloc_image(s, 48, 28, seed=300 + gi)
             c0 = util.alloc_image(d, 64, 36, seed=400 + gi)
-            a, b = util.copy_image(c0), util.copy_image(c0)
-            assert O.run_kernel(kernel, a, src, u) == 0
-            assert O.run_clref(kernel, b, src, u) == 0
-            for x, y in zip(a, b):
-                assert np.array_equal(x, y), f"{kernel} geometry {gi}"
+            yield f"layer/{kernel}/{gi}", kernel, src, c0, u
+
+
+def test_oracle_equals_compiled_reference_kernels():
+    """Kernel-body arithmetic of the restatement == the reference's OpenCL-C source compiled for
+    x86-64 (a cross-check, not a reference build: the image builtins are ours, oracle/clref/cl_shim.c).
+    Where oracle/_ref/libclref.so cannot be built, against the canvases it computed for the same cases
+    (tests/golden/clref_vectors.npz); where it can, it must also still reproduce that recording."""
+    rec = np.load(CLREF_GOLD)
+    live = O.clref() is not None
+    for key, kernel, src, c0, u in clref_layer_cases():
+        a = util.copy_image(c0)
+        assert O.run_kernel(kernel, a, src, u) == 0
+        b = [rec[f"{key}/out{i}"] for i in range(len(c0))]
+        if live:
+            lb = util.copy_image(c0)
+            assert O.run_clref(kernel, lb, src, u) == 0
+            for x, y in zip(lb, b):
+                assert np.array_equal(x, y), f"{key}: the compiled reference kernel no longer reproduces its recording"
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y), key
 
 
 def test_threaded_oracle_equals_single_thread():
