@@ -48,9 +48,10 @@ int split_stream_prefix(const DTick *ticks, const DLayer *layers, int n_ticks); 
 int fast_path_stream_bgra();
 int select_tail_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks);      // a lone tick's descriptors can travel as kernel arguments (ticks == layers == nullptr)
 int select_fast_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks, bool transient = false);   // transient: one tick, launched once
+// tables: the launch's geometry tables for the strip kernels (geom_cache.h; nullptr: none — they compute their geometry in place)
 hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *layers_host,
                             const DTick *ticks, const DLayer *layers, int n_ticks,
-                            int maxW, int maxH, hipStream_t stream);
+                            int maxW, int maxH, hipStream_t stream, GeomCache *tables);
 // kernels_idle.hip.cpp
 hipError_t launch_snd_s16i(int16_t *out, const int16_t *const *in, int count, int n, const float *gain, const float *fade, hipStream_t stream);
 hipError_t launch_me_fullsearch(const DPlane &out, const DPlane &ref, const DPlane &cur, const int32_t *block, const int32_t *window, const int32_t *image,
@@ -1223,27 +1224,26 @@ static int launch_transient(chv_context *c, const DTick &tick_in, const std::vec
     (void)hipGetLastError();   // the launchers report through hipGetLastError(): drop whatever an earlier, unrelated call left there
     if (fast_path_by_value(path) && desc_mode == 0) {
         // descriptors as kernel arguments: the ring is not involved
-        hipError_t e = launch_tick_fast(path, ht, hl, nullptr, nullptr, 1, ht->W, ht->H, c->stream);
+        hipError_t e = launch_tick_fast(path, ht, hl, nullptr, nullptr, 1, ht->W, ht->H, c->stream, nullptr);
         return e == hipSuccess ? CHV_OK : hip_fail(e, "kernel launch");
     }
     // The strip kernels take a lone tick of up to WAVE_ONE_LAYERS layers as an ARGUMENT (wave_common.hip.h: wave_one_descriptors; tick_bgra_wave_one): no ring
     // slot, no copy in front of the launch.  The layers are pointed at the device's geometry tables first, where its store has them for this
     // scene; a launch that is to BUILD tables (a scene's second sighting) needs its layers in device memory and goes through the slot below.
     const bool wave = fast_path_is_wave(path);
-    GeomTransient &gt = geom_transient_current();
-    gt.covered = false;
+    // what the store answered: built + patched where it pointed the layers at its tables for `config` (owns nothing, has no layer arrays)
+    GeomCache covered;
+    covered.owns = false; covered.n_layers = (int)layers.size();
     if (wave && desc_mode == 0 && wave_layers_by_value(tf, &tick, layers.data())) {
         WaveOne one;
         one.t = tick;
         memcpy(one.l, layers.data(), layers.size() * sizeof(DLayer));
         bool build = false;
-        gt.covered = geom_store_patch(tf, &one.t, one.l, 1, one.t.W, one.t.H, (int)layers.size(), &gt.cfg, &build);
+        covered.built = covered.patched = geom_store_patch(tf, &one.t, one.l, 1, one.t.W, one.t.H, covered.n_layers, &covered.config, &build);
         if (!build) {
-            hipError_t e = launch_tick_fast(path, &one.t, one.l, nullptr, nullptr, 1, one.t.W, one.t.H, c->stream);
-            gt.covered = false;
+            hipError_t e = launch_tick_fast(path, &one.t, one.l, nullptr, nullptr, 1, one.t.W, one.t.H, c->stream, &covered);
             return e == hipSuccess ? CHV_OK : hip_fail(e, "kernel launch");
         }
-        gt.covered = false;
     }
     DescSlot ds(c);
     if (ds.rc) return ds.rc;
@@ -1257,7 +1257,7 @@ static int launch_transient(chv_context *c, const DTick &tick_in, const std::vec
     // (not with CHV_DESC=host: a build would copy the slot onto itself)
     bool build_tables = false;
     if (wave && !layers.empty() && desc_mode != 1)
-        gt.covered = geom_store_patch(tf, st, sl, 1, st->W, st->H, (int)layers.size(), &gt.cfg, &build_tables);
+        covered.built = covered.patched = geom_store_patch(tf, st, sl, 1, st->W, st->H, covered.n_layers, &covered.config, &build_tables);
     DTick *dt = nullptr;
     if (desc_mode == 1) {
         HIP_TRY(hipHostGetDevicePointer((void **)&dt, st, 0));
@@ -1272,16 +1272,13 @@ static int launch_transient(chv_context *c, const DTick &tick_in, const std::vec
         // does) and gives them to the store — the next tick of the scene finds them before its descriptors are copied
         GeomCache tmp;
         tmp.d_layers = dl; tmp.h_layers = sl; tmp.n_layers = (int)layers.size(); tmp.force_build = true;
-        geom_cache_current() = &tmp;
-        e = launch_tick_fast(path, st, sl, dt, dl, 1, st->W, st->H, c->stream);
-        geom_cache_current() = nullptr;
+        e = launch_tick_fast(path, st, sl, dt, dl, 1, st->W, st->H, c->stream, &tmp);
         if (tmp.owns && tmp.tables) (void)hipStreamSynchronize(c->stream);          // (the store was full: the tables die with this launch)
         geom_cache_release(tmp);
     } else {
-        e = path >= 0 ? launch_tick_fast(path, st, sl, dt, dl, 1, st->W, st->H, c->stream)
+        e = path >= 0 ? launch_tick_fast(path, st, sl, dt, dl, 1, st->W, st->H, c->stream, &covered)
                       : launch_tick_general(tf, st, sl, dt, dl, 1, st->W, st->H, c->stream);
     }
-    geom_transient_current().covered = false;
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return CHV_OK;
 }
@@ -1660,21 +1657,15 @@ extern "C" int chv_batch_run(chv_context *c, chv_batch *b) {
         chv_batch *bb; hipStream_t st;
         ~BlockMark() { if (bb->blk.dev) { if (hipEventRecord(bb->blk.ev, st) == hipSuccess) bb->blk.last = st; else (void)hipGetLastError(); } }
     } mark{ b, c->stream };
-    // (the strip kernels' launcher finds the batch's geometry tables through this: geom_cache.h)
-    struct CacheScope {
-        explicit CacheScope(chv_batch *bb) {
-            bb->geom.d_layers = bb->d_layers; bb->geom.h_layers = bb->h_layers.data(); bb->geom.n_layers = (int)bb->h_layers.size();
-            geom_cache_current() = &bb->geom;
-        }
-        ~CacheScope() { geom_cache_current() = nullptr; }
-    } scope(b);
+    // (the layer arrays the strip kernels' launcher patches when it builds the batch's geometry tables: geom_cache.h)
+    b->geom.d_layers = b->d_layers; b->geom.h_layers = b->h_layers.data(); b->geom.n_layers = (int)b->h_layers.size();
     hipError_t e = b->fast_path >= 0
-        ? launch_tick_fast(b->fast_path, b->h_ticks.data(), b->h_layers.data(), b->d_ticks, b->d_layers, b->n_ticks, b->maxW, b->maxH, c->stream)
+        ? launch_tick_fast(b->fast_path, b->h_ticks.data(), b->h_layers.data(), b->d_ticks, b->d_layers, b->n_ticks, b->maxW, b->maxH, c->stream, &b->geom)
         : launch_tick_general(b->target_format, b->h_ticks.data(), b->h_layers.data(), b->d_ticks, b->d_layers, b->n_ticks, b->maxW, b->maxH, c->stream);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     if (b->fast_path2 != -2) {
         e = b->fast_path2 >= 0
-            ? launch_tick_fast(b->fast_path2, b->h_ticks2.data(), b->h_layers.data(), b->d_ticks2, b->d_layers, b->n_ticks, b->maxW, b->maxH, c->stream)
+            ? launch_tick_fast(b->fast_path2, b->h_ticks2.data(), b->h_layers.data(), b->d_ticks2, b->d_layers, b->n_ticks, b->maxW, b->maxH, c->stream, &b->geom)
             : launch_tick_general(b->target_format, b->h_ticks2.data(), b->h_layers.data(), b->d_ticks2, b->d_layers, b->n_ticks, b->maxW, b->maxH, c->stream);
         if (e != hipSuccess) return hip_fail(e, "kernel launch (second part of the batch)");
     }

@@ -43,8 +43,10 @@ bool bgra_stream_eligible(const DTick *ticks, const DLayer *layers, int n_ticks)
 hipError_t launch_bgra_stream(const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int maxW, int maxH, hipStream_t stream);
 bool yuv_stream_eligible(int tf, const DTick *ticks, const DLayer *layers, int n_ticks, bool transient);
 hipError_t launch_yuv_stream(int tf, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int maxW, int maxH, hipStream_t stream);
+// (tables: the launch's geometry tables, geom_cache.h; nullptr: none)
+struct GeomCache;
 hipError_t launch_wave_layers(int target_format, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers,
-                              int n_ticks, int maxW, int maxH, hipStream_t stream);
+                              int n_ticks, int maxW, int maxH, hipStream_t stream, GeomCache *tables);
 
 #ifndef CHV_TW
 #define CHV_TW 128
@@ -565,7 +567,7 @@ bool fast_path_by_value(int path) { return path == FP_STREAM || path == FP_STREA
 
 hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *layers_host,
                             const DTick *ticks, const DLayer *layers, int n_ticks,
-                            int maxW, int maxH, hipStream_t stream) {
+                            int maxW, int maxH, hipStream_t stream, GeomCache *tables) {
     if (path == FP_CLEAR_BGRA) {
         const DTick &T = ticks_host[0];
         if (T.W <= 0 || T.H <= 0) return hipSuccess;
@@ -575,9 +577,9 @@ hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *lay
     if (path == FP_STREAM) return launch_bgra_stream(ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream);
     if (path == FP_STREAM_NV12) return launch_yuv_stream(TF_NV12, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream);
     if (path == FP_STREAM_Y420P) return launch_yuv_stream(TF_Y420P, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream);
-    if (path == FP_WAVE_LAYERS) return launch_wave_layers(TF_BGRA, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream);
-    if (path == FP_WAVE_NV12) return launch_wave_layers(TF_NV12, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream);
-    if (path == FP_WAVE_Y420P) return launch_wave_layers(TF_Y420P, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream);
+    if (path == FP_WAVE_LAYERS) return launch_wave_layers(TF_BGRA, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream, tables);
+    if (path == FP_WAVE_NV12) return launch_wave_layers(TF_NV12, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream, tables);
+    if (path == FP_WAVE_Y420P) return launch_wave_layers(TF_Y420P, ticks_host, layers_host, ticks, layers, n_ticks, maxW, maxH, stream, tables);
     if (path != FP_NV12_BGRA_TILED && path != FP_Y420P_BGRA_TILED) return hipErrorNotSupported;
     const bool clear = ticks_host[0].clear_first != 0, planar = path == FP_Y420P_BGRA_TILED;
     const int tiles_x = (maxW + TW - 1) / TW;

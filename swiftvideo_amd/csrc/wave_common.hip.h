@@ -4,16 +4,13 @@
 // design and the measurements behind it.
 #pragma once
 #include "tile_common.hip.h"
+#include "geom_cache.h"
 
 #pragma clang fp contract(off)
 
 namespace chv {
 
-constexpr int WTW = 64;                 // strip width: one lane per column
-// 1: layers of a batch take their per-strip geometry from the batch's tables (geom_cache.h, WaveStrip::setup_cached); 0: always computed in place
-#ifndef CHV_GEOM_CACHE
-#define CHV_GEOM_CACHE 1
-#endif
+// (WTW, the strip width, and CHV_GEOM_CACHE: geom_cache.h)
 
 // Waves per block.  The waves of a block share nothing but the launch (every wave has its own LDS region and there is no block
 // barrier on the data path), so the block size only sets the granularity at which LDS is handed out: one wave per block
@@ -337,21 +334,17 @@ CHV_DEV bool src_is_planar(int kind) { return kind == LK_BGRA_FROM_Y420P || kind
 // One table per geometry class of a batch (same matrices, source plane sizes, canvas size), built by geom_precompute (kernels_wave_yuv.hip.cpp)
 // with setup() itself and read back by setup_cached() in the CACHED instantiations of the tick kernels — which contain no set-up code at all.
 // A table covers every strip of its canvas, staged or not.  A DLayer carries its class's table address in pad2 (0: none).
-struct GeomHdr { int32_t strips_x, strips_y, wth, row_bytes; uint32_t flags_off, cols_off, rows_off, pad; };     // 32 bytes, at the table's base
+// (the header, GeomHdr, and the job list of geom_precompute, GeomJob: geom_cache.h)
 struct GeomCol {                       // a strip column: the lanes' column entries and the column halves of the rectangles
     uint4 a[64];                       // staged form: { cyo, cco, bits(cya), bits(cca) }
     uint4 b[64];                       // { tap-0 column of the unstaged form (luma / RGB), (chroma), cfl, - }
     int32_t s[16];                     // g0.b0, g0.nvec, inv20(nvec), inv20(nvec + 2), then the same four of g1
 };
+static_assert(sizeof(GeomCol) == kGeomColBytes, "the host lays the tables out with kGeomColBytes per strip column");
 // a strip row (row_bytes each): uint4 rowtab[3 * WTH] as setup() leaves it in LDS for a STAGED layer, the same for an unstaged one (row
 // positions instead of LDS offsets), then int32 s[16]: g0.r_lo, g0.rows, g0.pair, g0.r_hi1, the same four of g1, unit_rows
 enum : uint32_t { GF_STAGED = 1, GF_ALL_INSIDE = 2, GF_EDGE0 = 4, GF_EDGE1 = 8 };       // the flag word of a strip (row-major, strips_x per row)
 struct GeomRaw { int cy, cc, ry, rc, rfl; float rya, rca; };      // (setup<true>: what the unstaged form is made of)
-struct GeomJob {                       // one class for geom_precompute: a representative layer (its plane POINTERS are not used), the canvas, the table
-    DLayer layer;
-    int32_t W, H, strips_x, strips_y, first_block, pad;
-    uint8_t *table;
-};
 
 template <int WTH, int INTERIOR = 0, int KINDS = 7>
 struct WaveStrip {

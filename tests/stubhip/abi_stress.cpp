@@ -49,6 +49,13 @@ static chv_uniforms full_canvas(float opacity) {
     u.opacity = opacity; u.output_size[0] = 64; u.output_size[1] = 32; u.input_size[0] = 64; u.input_size[1] = 32;
     return u;
 }
+// a counter of the geometry-table store of `c`'s device (chv_debug_get_counter reads the current device's: chv_pass_end makes `c`'s current)
+static unsigned long long store_counter(chv_context *c, const char *name) {
+    unsigned long long v = 0;
+    CK(chv_pass_end(c, 1));
+    CK(chv_debug_get_counter(name, &v));
+    return v;
+}
 static chv_layer layer_of(int kernel, const Pic &p, float opacity) {
     chv_layer l; memset(&l, 0, sizeof l);
     l.kernel = kernel; l.image = p.img; l.uniforms = full_canvas(opacity);
@@ -89,6 +96,8 @@ static void single_thread(chv_context *c) {
     // the descriptor ring wraps: 300 ring-route launches without a host wait, each with descriptors of its own
     for (int i = 0; i < 300; i++) { mixed[2].uniforms.opacity = i / 300.f; CK(chv_composite(c, &canvas.img, 0, mixed, 3)); }
     CK(chv_pass_end(c, 1));
+    // ... of one scene through the strip route (opacity lies outside the geometry): the device's store built its tables and pointed ticks at them
+    EXPECT(store_counter(c, "geom_store_builds") > 0 && store_counter(c, "geom_store_patched") > 0);
     // batches: plain, split ("videos, then something else"), run several times, destroyed with work in flight behind them
     chv_layer split[5] = { vids[0], vids[1], vids[2], vids[3], mixed[2] };
     chv_tick ticks[6]; memset(ticks, 0, sizeof ticks);
@@ -262,8 +271,10 @@ static void single_thread(chv_context *c) {
 }
 
 // what the Swift host's threads do: a mixer per thread on a context of its own (mix.video.swift:55,99), an uploader and a downloader on theirs
-// (compute.swift:177,234), buffers released from whatever thread drops the last reference (compute.cl.swift:55-57)
+// (compute.swift:177,234), buffers released from whatever thread drops the last reference (compute.cl.swift:55-57).  The two-layer tick is one
+// scene through the strip route from every thread: the device's store is looked up and built concurrently.
 static void many_threads(chv_context *parent, int n_threads) {
+    const unsigned long long builds = store_counter(parent, "geom_store_builds"), patched = store_counter(parent, "geom_store_patched");
     std::vector<std::thread> th;
     std::vector<std::atomic<chv_buffer *>> orphans((size_t)n_threads * 8);
     for (auto &o : orphans) o.store(nullptr);
@@ -314,6 +325,7 @@ static void many_threads(chv_context *parent, int n_threads) {
     });
     for (auto &t : th) t.join();
     reaper.join();
+    EXPECT(store_counter(parent, "geom_store_builds") > builds && store_counter(parent, "geom_store_patched") > patched);
 }
 
 int main(int argc, char **argv) {

@@ -42,6 +42,7 @@ hipError_t hipGetDeviceCount(int *n);
 hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int dev);
 hipError_t hipDeviceGetPCIBusId(char *buf, int len, int dev);
 hipError_t hipSetDevice(int dev);
+hipError_t hipGetDevice(int *dev);
 hipError_t hipGetLastError();
 const char *hipGetErrorString(hipError_t e);
 hipError_t hipMalloc(void **p, size_t n);

@@ -1,10 +1,12 @@
-// tests/stubhip/stub_launchers.cpp — stand-ins for what chipvideo.cpp imports from the kernel translation units (path selection and
-// launchers), for the sanitizer builds of the host runtime (tests/test_sanitizers.py).  TEST INFRASTRUCTURE.
+// tests/stubhip/stub_launchers.cpp — stand-ins for what chipvideo.cpp and geom_store.cpp import from the kernel translation units (path selection,
+// launchers, the strip kernels' launch configuration), for the sanitizer builds of the host runtime (tests/test_sanitizers.py).  TEST INFRASTRUCTURE.
 //
 // A "launch" is a closure on the stream (stub_runtime.cpp) that, when the stream gets to it, reads the tick and layer descriptors it was given,
 // checks them, touches the first and last byte of every plane they name (so a buffer freed or a descriptor slot recycled too early is a
 // sanitizer report) and stamps the canvas.  Launches whose descriptors the host still owns at launch time (launch_tick_fast: the host copies)
 // remember a checksum and compare it with what the DEVICE copy holds when the launch runs: a ring slot overwritten in flight is an abort.
+// The geometry tables are the product's own (geom_store.cpp): a "kernel" also reads a byte of every table its layers point at, so that a table
+// freed under a launch in flight is a sanitizer report.
 // Path selection keeps the product's shape where the host logic depends on it: BGRA ticks of 1..4 YUV layers on a cleared canvas take the
 // by-value route (kernel arguments, no descriptor copy), everything else with layers the ring + device-twin route, layerless clears their
 // own; CHV_FORCE_GENERAL sends everything to launch_tick_general.
@@ -17,9 +19,6 @@
 #include "../../swiftvideo_amd/csrc/device_types.h"
 #include "../../swiftvideo_amd/csrc/switches.h"
 #include "../../swiftvideo_amd/csrc/geom_cache.h"
-#include <map>
-#include <mutex>
-#include <cstring>
 
 namespace chv {
 enum { FP_NONE = -1, FP_WAVE = 2, FP_STREAM = 5, FP_CLEAR = 6 };
@@ -41,6 +40,7 @@ static void run_tick(const DTick &T, const DLayer *L) {
         const DLayer &Y = L[T.first_layer + l];
         if (Y.kind < 0 || Y.kind > 7) { fprintf(stderr, "stub kernel: corrupt layer descriptor (kind %d)\n", Y.kind); abort(); }
         for (int p = 0; p < 3; p++) touch(Y.src.pl[p], false);
+        if (const void *tab = geom_table(Y)) { volatile const uint8_t *t = (const uint8_t *)tab; (void)*t; }
     }
     for (int p = 0; p < 3; p++) touch(T.dst.pl[p], true);
 }
@@ -69,27 +69,36 @@ static hipError_t enqueue_ticks(const DTick *ticks_host, const DLayer *layers_ho
     return hipSuccess;
 }
 
-GeomCache *&geom_cache_current() { static thread_local GeomCache *cur = nullptr; return cur; }
-void geom_cache_release(GeomCache &) {}                    // (the stand-in launchers build no tables)
-// A stand-in for the device's store of tables (geom_cache.h), so that the library's hooks run under the sanitizers: the second launch of a scene
-// "builds" (chipvideo.cpp hands its launch a temporary GeomCache), from the third one on its layers are "covered" (pointed at a table).
-GeomTransient &geom_transient_current() { static thread_local GeomTransient t; return t; }
-bool geom_store_patch(int, const DTick *ticks_host, DLayer *layers_host, int n_ticks, int, int, int n_layers_total, GeomConfig *cfg, bool *want_build) {
-    static std::mutex mu;
-    static std::map<uint64_t, int> seen;
-    uint64_t h = 1469598103934665603ull;
+// the source classes of a launch as the strip kernels' planner counts them: bit 0 NV12, bit 1 y420p, bit 2 RGB, bit 3 applied per pixel
+static int wave_kinds(const DTick *ticks, const DLayer *layers, int n_ticks) {
+    int kinds = 0;
     for (int i = 0; i < n_ticks; i++)
-        for (int l = 0; l < ticks_host[i].n_layers; l++) h = h * 1099511628211ull ^ fnv(layers_host[ticks_host[i].first_layer + l].u, sizeof layers_host[0].u);
-    int c;
-    { std::lock_guard<std::mutex> lk(mu); c = ++seen[h]; }
-    memset(cfg, 0, sizeof *cfg);
-    cfg->n_layers = n_layers_total;
-    *want_build = c == 2;
-    for (int i = 0; i < n_ticks; i++)
-        for (int l = 0; l < ticks_host[i].n_layers; l++) { DLayer &L = layers_host[ticks_host[i].first_layer + l]; L.pad2[0] = c >= 3 ? 0x1000 : 0; L.pad2[1] = 0; }
-    return c >= 3;
+        for (int l = 0; l < ticks[i].n_layers; l++) {
+            const DLayer &L = layers[ticks[i].first_layer + l];
+            if (L.kind == LK_BGRA_METAL || (L.flags & (LF_AXIS_ALIGNED | LF_BOUNDED)) != (LF_AXIS_ALIGNED | LF_BOUNDED)) kinds |= 8;
+            else kinds |= L.kind == LK_BGRA_FROM_RGB || L.kind == LK_YUV_FROM_RGB || L.kind == LK_YUV_FROM_RGB_INT ? 4 : L.kind == LK_BGRA_FROM_Y420P || L.kind == LK_YUV_FROM_Y420P ? 2 : 1;
+        }
+    return kinds;
 }
-uint64_t geom_store_counter(int) { return 0; }
+// a fixed launch configuration from the canvas size and the layers' classes
+bool wave_geom_config(int target_format, const DTick *ticks_host, const DLayer *layers_host, int n_ticks, int maxW, int maxH, int n_layers_total, GeomConfig *cfg) {
+    const int kinds = wave_kinds(ticks_host, layers_host, n_ticks), yuv = (kinds & 3) ? 1 : 0;
+    *cfg = GeomConfig{ target_format, 8, 320, 12, yuv * 96, yuv * 8, (kinds & 2) ? 1 : 0, (maxW + WTW - 1) / WTW, (maxH + 7) / 8, n_layers_total };
+    return kinds != 4 && (kinds & 7) != 0;
+}
+// the tables' builder: reads the job list and writes each job's table header when the stream gets to it (not a tick launch: it does not ask
+// stubhip_launch_should_fail, by which the tests count and fail launches)
+hipError_t launch_geom_precompute(const GeomConfig &cfg, const GeomJob *jobs, int n_jobs, int, hipStream_t stream) {
+    stubhip_enqueue(stream, [=] {
+        for (int j = 0; j < n_jobs; j++) {
+            GeomHdr H;
+            memcpy(&H, jobs[j].table, sizeof H);
+            if (H.strips_x != jobs[j].strips_x || H.strips_y != jobs[j].strips_y || H.wth != cfg.wth) { fprintf(stderr, "stub geom_precompute: table header and job differ\n"); abort(); }
+            memcpy(jobs[j].table, &H, sizeof H);
+        }
+    });
+    return hipSuccess;
+}
 bool fast_path_is_wave(int path) { return path == FP_WAVE; }
 bool wave_layers_by_value(int, const DTick *t, const DLayer *) { return t->n_layers >= 1 && t->n_layers <= WAVE_ONE_LAYERS; }
 const char *bgra_wave_build_flags() { return "stub:abl=0"; }
@@ -131,12 +140,22 @@ int select_fast_path(int target_format, const DTick *ticks, const DLayer *layers
     return FP_WAVE;
 }
 int select_tail_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks) { return select_fast_path(target_format, ticks, layers, n_ticks, false); }
-hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int, int, hipStream_t stream) {
+hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int maxW, int maxH,
+                            hipStream_t stream, GeomCache *tables) {
     if (path == FP_CLEAR) {
         if (stubhip_launch_should_fail()) return hipErrorLaunchFailure;
         DPlane d = ticks_host[0].dst.pl[0];
         stubhip_enqueue(stream, [d] { touch(d, true); });
         return hipSuccess;
+    }
+    if (path == FP_WAVE && tables && wave_kinds(ticks_host, layers_host, n_ticks) != 4) {
+        // as launch_wave_layers: the launch's tables for its configuration, in front of the kernel (the canvas's planes tell its format)
+        const DImage &dst = ticks_host[0].dst;
+        GeomConfig cfg;
+        bool cached = false;
+        wave_geom_config(dst.pl[2].ptr ? TF_Y420P : dst.pl[1].ptr ? TF_NV12 : TF_BGRA, ticks_host, layers_host, n_ticks, maxW, maxH, tables->n_layers, &cfg);
+        hipError_t e = geom_cache_prepare(*tables, cfg, ticks_host, n_ticks, stream, &cached);
+        if (e != hipSuccess) return e;
     }
     return enqueue_ticks(ticks_host, layers_host, ticks, layers, n_ticks, stream);
 }

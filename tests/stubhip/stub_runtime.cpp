@@ -84,6 +84,7 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int dev) {
 }
 hipError_t hipDeviceGetPCIBusId(char *buf, int len, int dev) { snprintf(buf, (size_t)len, "0000:%02x:00.0", 5 + dev); return hipSuccess; }
 hipError_t hipSetDevice(int dev) { if (dev < 0 || dev >= device_count()) return err(hipErrorInvalidDevice); t_device = dev; return hipSuccess; }
+hipError_t hipGetDevice(int *dev) { *dev = t_device; return hipSuccess; }
 hipError_t hipGetLastError() { hipError_t e = t_last; t_last = hipSuccess; return e; }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorLaunchFailure ? "launch failure (injected)" : "stub error"; }
 

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../swiftvideo_amd/csrc"
 OBJ=../../variants/obj_$NAME
 mkdir -p $OBJ
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -w -DCHV_ARCH=\"gfx950\" -DCHV_HIPCC_VERSION=\"variant\""
-for f in chipvideo.cpp kernels_*.hip.cpp; do cp ${f%.cpp}.o $OBJ/; done
+for f in chipvideo.cpp geom_store.cpp kernels_*.hip.cpp; do cp ${f%.cpp}.o $OBJ/; done
 for FILE in "$@"; do
   git show HEAD:swiftvideo_amd/csrc/$FILE > head_tmp_$FILE
   /opt/rocm/bin/hipcc $FLAGS -x hip -c head_tmp_$FILE -o $OBJ/${FILE%.cpp}.o || { rm -f head_tmp_$FILE; exit 1; }
