@@ -273,7 +273,9 @@ typedef struct chv_me_uniforms {      /* MotionEstimationUniforms, kernels.metal
  * `img_clear_* + N layer kernels on one target`, what an unchanged VideoMixer issues per tick (mix.video.swift:116-124), leaves as the ONE
  * launch chv_composite would have made of it: same bytes (that equality is chv_composite's definition), one launch instead of N + 1.  What is
  * held goes out, in issue order, at chv_pass_end — or before anything else that touches ctx's stream: an upload or download through ctx, a
- * batch, a custom or buffer kernel, an event, chv_context_stream, a kernel on another target, a clear after layers.  Buffers named by held
+ * batch, a custom or buffer kernel, an event, chv_context_stream, a kernel on another target, a clear after layers, a layer whose
+ * input shares device memory with the held target (compared by the planes' address ranges: the target itself, another handle wrapped over its
+ * memory, a view of it with plane offsets — such a layer samples what the kernels issued before it wrote).  Buffers named by held
  * kernels may be passed to chv_buffer_free before the pass ends (a ComputeBuffer's deinit can run as soon as runComputeKernel returns,
  * compute.cl.swift:55-57): the free takes effect once they have been launched.  Work of OTHER contexts is ordered against a pass's kernels at the
  * pass's end, as against any kernel: events, or the per-buffer upload events.  Brackets nest (uploadComputePicture opens its own around its

@@ -950,6 +950,17 @@ static int plane_to_device(const chv_plane &p, int comps, int device, DPlane *ou
     return CHV_OK;
 }
 
+// do two planes (both accepted by plane_to_device) share device memory?  A plane spans ptr + offset .. + (height - 1) * pitch + row bytes;
+// two handles over one piece of memory (chv_buffer_wrap) and views with plane offsets are compared by what they address
+static bool planes_overlap(const chv_plane &a, const chv_plane &b) {
+    if (!buf_ok(a.buffer) || !buf_ok(b.buffer) || a.buffer->device != b.buffer->device) return false;
+    if (a.width <= 0 || a.height <= 0 || b.width <= 0 || b.height <= 0) return false;
+    const uintptr_t a0 = (uintptr_t)a.buffer->ptr + a.offset, b0 = (uintptr_t)b.buffer->ptr + b.offset;
+    const uintptr_t a1 = a0 + (size_t)(a.height - 1) * a.pitch + (size_t)a.width * a.components;
+    const uintptr_t b1 = b0 + (size_t)(b.height - 1) * b.pitch + (size_t)b.width * b.components;
+    return a0 < b1 && b0 < a1;
+}
+
 static int target_to_device(const chv_image *t, int target_format, int device, DImage *out) {
     if (!t) return fail(CHV_ERR_BAD_TARGET, "null target");
     static const int np[3] = { 2, 3, 1 };
@@ -1461,11 +1472,13 @@ extern "C" int chv_run_kernel(chv_context *c, int kernel, const chv_image *targe
         chv_context::PendingPass &pp = c->pending;
         // ... and so does a layer that READS the canvas being held (issued kernel by kernel it would sample what the held layers wrote; inside one
         // fused launch the canvas lives in registers and memory still has the old bytes), and a pass deeper than a batch's descriptor allows
+        // (by device ADDRESS RANGE, not by handle: a second chv_buffer_wrap over the canvas's memory, or a view with plane offsets, reads it too)
         bool reads_held_canvas = false;
         if (pp.active && !s.is_clear)
-            for (int i = 0; i < inputs[0].n_planes && i < 3; i++)
-                for (int k = 0; k < pp.target.n_planes && k < 3; k++)
-                    reads_held_canvas = reads_held_canvas || inputs[0].planes[i].buffer == pp.target.planes[k].buffer;
+            for (int n = 0; n < n_inputs; n++)
+                for (int i = 0; i < inputs[n].n_planes && i < 3; i++)
+                    for (int k = 0; k < pp.target.n_planes && k < 3; k++)
+                        reads_held_canvas = reads_held_canvas || planes_overlap(inputs[n].planes[i], pp.target.planes[k]);
         if (pp.active && (s.is_clear || reads_held_canvas || pp.layers.size() >= 1024 || !same_target(pp.target, *target) || (pp.clear_tf >= 0 && pp.clear_tf != tf)))
             FLUSH_PENDING(c);
         if (!pp.active) {

@@ -217,6 +217,31 @@ static void single_thread(chv_context *c) {
         EXPECT(stubhip_launches() == l0 + 1);
         CK(chv_pass_end(c, 1));
         EXPECT(stubhip_launches() == l0 + 2);
+        // ... also when it reads the canvas through ANOTHER handle over the same memory (chv_buffer_wrap) or through a view of it with a plane
+        // offset of its own: the held canvas is recognised by the address range of its planes; a picture elsewhere in memory is held as before
+        {
+            void *dev = nullptr; size_t bytes = 0;
+            CK(chv_buffer_info(canvas.buf, &dev, &bytes));
+            chv_buffer *again = nullptr;
+            CK(chv_buffer_wrap(c, dev, bytes, &again));
+            const int32_t pitch = canvas.img.planes[0].pitch;
+            chv_image alias = canvas.img, right_half = canvas.img, last_rows = canvas.img;
+            alias.planes[0].buffer = again;
+            right_half.width = W / 2; right_half.planes[0] = chv_plane{ again, (size_t)W * 2, W / 2, H, pitch, 4 };
+            last_rows.height = 2; last_rows.planes[0] = chv_plane{ canvas.buf, (size_t)(H - 2) * pitch, W, 2, pitch, 4 };
+            const chv_image *sources[4] = { &alias, &right_half, &last_rows, &rgb.img };
+            for (const chv_image *src : sources) {
+                l0 = stubhip_launches();
+                CK(chv_pass_begin(c));
+                CK(chv_run_kernel(c, CHV_K_IMG_CLEAR_BGRA, &canvas.img, nullptr, 0, nullptr, 0, 0, nullptr));
+                CK(chv_run_kernel(c, CHV_K_IMG_BGRA_BGRA_TX, &canvas.img, &rgb.img, 1, &us[0], sizeof us[0], 1, nullptr));
+                CK(chv_run_kernel(c, CHV_K_IMG_BGRA_BGRA_TX, &canvas.img, src, 1, &us[1], sizeof us[1], 1, nullptr));
+                EXPECT(stubhip_launches() == l0 + (src == &rgb.img ? 0 : 1));
+                CK(chv_pass_end(c, 1));
+                EXPECT(stubhip_launches() == l0 + (src == &rgb.img ? 1 : 2));
+            }
+            CK(chv_buffer_free(again));
+        }
         CK(chv_pass_begin(c));
         for (int l = 0; l < 2100; l++) CK(chv_run_kernel(c, CHV_K_IMG_BGRA_BGRA_TX, &canvas.img, &rgb.img, 1, &us[l & 3], sizeof us[0], 1, nullptr));
         CK(chv_pass_end(c, 1));

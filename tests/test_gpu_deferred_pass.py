@@ -257,3 +257,48 @@ def test_random_passes_deferred_equals_kernel_by_kernel(ctx, seed):
             assert O.run_kernel(k, exp[t], srcs[t][i], u) == 0
     for a, e, f in zip(results[0], exp, fmts):
         G.assert_same(a, e, f"{f} vs oracle, ops {ops}")
+
+
+def _alias_of_left_half(ctx, canvas, cw, ch, how):
+    """a BGRA picture of the canvas's left half that shares its memory: a view through the canvas's own handle and its plane offset, or through
+    a SECOND handle wrapped over the same device memory (chv_buffer_wrap)"""
+    img = canvas.imageBuffer()
+    buf = img.computeTextures[0]
+    if how == "second_wrap":
+        lib = cv.load()
+        ptr, wrapped = C.c_void_p(), C.c_void_p()
+        cv.check(lib.chv_buffer_info(buf._h, C.byref(ptr), None))
+        cv.check(lib.chv_buffer_wrap(ctx.handle, ptr, buf.size, C.byref(wrapped)))
+        buf = sv.ComputeBuffer(wrapped.value, buf.size)
+    proto = sv.createPictureSample((cw // 2, ch), sv.PixelFormat.BGRA).imageBuffer()
+    return sv.PictureSample(proto.withChanges(computeTextures=[buf], gpuPitches=[img.gpuPitches[0]], gpuOffsets=[img.gpuOffsets[0]],
+                                              buffers=[], bufferType="gpu"))
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("how", ["view", "second_wrap"])
+def test_a_layer_that_reads_the_held_canvas_through_another_handle(ctx, how, mode):
+    """pass: clear, X -> the canvas's left half, then the LEFT HALF ITSELF (a view of the canvas, or a second handle over its memory) -> the right
+    half.  What the last layer reads and what it writes are disjoint, so the kernel-by-kernel result is defined: the left half as X painted it.
+    A held pass must send the canvas out before that layer — it is recognised by the memory its planes address, not by its handle."""
+    cw, ch = 128, 36
+    hw = cw // 2
+    x = util.alloc_image("nv12", 96, 54, seed=41)
+    ux = util.make_uniforms((cw, ch), rect=(0, 0, hw, ch), in_size=(96, 54))
+    ub = util.make_uniforms((cw, ch), rect=(hw, 0, hw, ch), opacity=0.8, in_size=(hw, ch))
+    exp = util.alloc_image("bgra", cw, ch, seed=42)
+    canvas = G.to_gpu(ctx, "bgra", cw, ch, util.copy_image(exp))
+    gx = G.to_gpu(ctx, "nv12", 96, 54, x)
+    assert O.run_kernel("img_clear_bgra", exp) == 0 and O.run_kernel("img_nv12_bgra", exp, x, ux) == 0
+    left = [np.ascontiguousarray(exp[0][:, :hw, :])]                      # the oracle's canvas after X: what the last layer samples
+    assert O.run_kernel("img_bgra_bgra_tx", exp, left, ub) == 0
+    assert np.array_equal(exp[0][:, :hw, :], left[0]), "the last layer must not write what it reads"
+    alias = _alias_of_left_half(ctx, canvas, cw, ch, how)
+    K = sv.ComputeKernel
+
+    def body(c):
+        c = sv.runComputeKernel(c, images=[], target=canvas, kernel=K.img_clear_bgra)
+        c = sv.runComputeKernel(c, images=[gx], target=canvas, kernel=K.img_nv12_bgra, uniforms=ux, blends=True)
+        return sv.runComputeKernel(c, images=[alias], target=canvas, kernel=K.img_bgra_bgra_tx, uniforms=ub, blends=True)
+    _issue(ctx, mode, body)
+    G.assert_same(G.from_gpu(ctx, canvas, "bgra", cw, ch), exp, f"{how}, {mode}")

@@ -606,12 +606,8 @@ def test_random_mixed_ticks(ctx, path, seed):
         G.assert_same(G.from_gpu(ctx, gd, "bgra", cw, ch), exp, f"seed {seed} tick {i} ({len(ticks[i][2])} layers) via {name}")
 
 
-@pytest.mark.parametrize("seed", range(24))
-def test_random_rgb_only_ticks(ctx, path, seed):
-    """Launches of RGB layers only — the instantiation of tick_bgra_wave that fills interior rectangles by LDS-DMA (kernels_wave.hip.cpp,
-    CHV_WAVE_DMA): canvases several strips wide and tall, so that strips lie inside a layer (DMA), on its edge and across the picture's edge
-    (the register path), layers of BGRA (DMA) and RGBA (byte swap: register path) pictures in one tick, stacks that share their predecessor's
-    geometry, up- and downscales between 3:1 and 1:3 (rows per DMA instruction from 1 to 16, the pair form beyond 1.6:1)."""
+def _random_rgb_only_ticks(ctx, seed):
+    """the ticks of test_random_rgb_only_ticks -> (ticks, expected canvases, (canvas, w, h))"""
     rng = np.random.default_rng(9500 + seed)
     clear = bool(rng.integers(0, 2))
     ticks, exps, gds = [], [], []
@@ -646,6 +642,16 @@ def test_random_rgb_only_ticks(ctx, path, seed):
         ticks.append((gd, clear, layers))
         exps.append(exp)
         gds.append((gd, cw, ch))
+    return ticks, exps, gds
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_random_rgb_only_ticks(ctx, path, seed):
+    """Launches of RGB layers only — the instantiation of tick_bgra_wave that fills interior rectangles by LDS-DMA (kernels_wave.hip.cpp,
+    CHV_WAVE_DMA): canvases several strips wide and tall, so that strips lie inside a layer (DMA), on its edge and across the picture's edge
+    (the register path), layers of BGRA (DMA) and RGBA (byte swap: register path) pictures in one tick, stacks that share their predecessor's
+    geometry, up- and downscales between 3:1 and 1:3 (rows per DMA instruction from 1 to 16, the pair form beyond 1.6:1)."""
+    ticks, exps, gds = _random_rgb_only_ticks(ctx, seed)
     h, name, keep = G.make_batch(ctx, ticks)
     assert name == WAVE, name
     G.run_batch(ctx, h)

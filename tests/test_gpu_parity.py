@@ -118,17 +118,23 @@ def test_fused_tick_equals_sequential_and_oracle(ctx, dst_fmt):
 
 
 def test_pitched_planes_and_padding_untouched(ctx):
-    """Device planes are 256-byte pitched; host planes may carry their own stride."""
+    """Device planes are 128-byte pitched; host planes may carry their own stride.  The pictures lie behind guards (tests/layouts.py, the
+    `guarded` layout: uploadComputePicture's offsets and pitches, every byte that is not payload a sentinel), and both allocations are read back
+    completely: the launch wrote payload bytes of its target and nothing else — no pitch padding, nothing in front or behind, not its source."""
+    import layouts as L
     cw, ch, iw, ih = 50, 22, 36, 20
     src = util.alloc_image("nv12", iw, ih, seed=3, pad=12)
     canvas0 = util.alloc_image("nv12", cw, ch, seed=4, pad=6)
     u = util.make_uniforms((cw, ch), rect=(3, 2, 40, 18), opacity=0.8, in_size=(iw, ih))
     exp = util.copy_image(canvas0)
     assert O.run_kernel("img_nv12_nv12", exp, src, u) == 0
-    gs, gd = G.to_gpu(ctx, "nv12", iw, ih, src), G.to_gpu(ctx, "nv12", cw, ch, canvas0)
+    rec = L.Recorder()
+    gs, gd = L.place(ctx, "nv12", iw, ih, src, "guarded", 1, recorder=rec), L.place(ctx, "nv12", cw, ch, canvas0, "guarded", 2, recorder=rec)
+    assert all(p.pitch == 128 and p.pitch > p.row for s in (gs, gd) for p in rec.placement(s).planes)
     sv.usingContext(ctx, lambda c: sv.runComputeKernel(c, images=[gs], target=gd,
                                                        kernel=sv.ComputeKernel.img_nv12_nv12, uniforms=u, blends=True))
-    G.assert_same(G.from_gpu(ctx, gd, "nv12", cw, ch), exp, "pitched nv12")
+    G.assert_same(L.from_gpu(rec, G.from_gpu, ctx, gd, "nv12", cw, ch), exp, "pitched nv12")
+    assert rec.sweep(ctx) == 2
 
 
 def test_error_behaviour(ctx):

@@ -159,15 +159,14 @@ def test_rotated_overlay_stays_in_the_wave_kernel(ctx, rows, d):
     assert run_yuv_tick(ctx, d, 384, 216, True, specs, expect=None) == f"tick_yuv_wave<{d}>"
 
 
-@pytest.mark.parametrize("seed", list(range(32)) + [f"int{i}" for i in range(16)])
-def test_random_yuv_ticks(ctx, rows, seed):
-    """Seeded random ticks on 4:2:0 canvases: 1..8 layers of random source kinds with random axis-aligned geometry, three ticks
-    of different (even) sizes per launch.  Seeds `int<n>`: the RGB layers through the integer-matrix kernels, a random colourspace each."""
+def _random_yuv_ticks(ctx, seed, clear=None):
+    """the ticks of test_random_yuv_ticks -> (canvas format, seed as a number, ticks, expected canvases, (canvas, w, h)); `clear`: instead of the drawn one"""
     integer = isinstance(seed, str)
     seed = int(seed[3:]) + 100 if integer else seed
     rng = np.random.default_rng(11000 + seed)
     d = "nv12" if seed % 2 == 0 else "y420p"
-    clear = bool(rng.integers(0, 2))
+    drawn = bool(rng.integers(0, 2))
+    clear = drawn if clear is None else clear
     kinds = {"nv12": ["img_nv12_nv12", "img_y420p_nv12", "img_bgra_nv12", "img_rgba_nv12"],
              "y420p": ["img_y420p_y420p", "img_bgra_y420p", "img_rgba_y420p"]}[d]
     if integer:
@@ -207,6 +206,14 @@ def test_random_yuv_ticks(ctx, rows, seed):
         ticks.append((gd, clear, layers))
         exps.append(exp)
         gds.append((gd, cw, ch))
+    return d, seed, ticks, exps, gds
+
+
+@pytest.mark.parametrize("seed", list(range(32)) + [f"int{i}" for i in range(16)])
+def test_random_yuv_ticks(ctx, rows, seed):
+    """Seeded random ticks on 4:2:0 canvases: 1..8 layers of random source kinds with random axis-aligned geometry, three ticks
+    of different (even) sizes per launch.  Seeds `int<n>`: the RGB layers through the integer-matrix kernels, a random colourspace each."""
+    d, seed, ticks, exps, gds = _random_yuv_ticks(ctx, seed)
     h, name, keep = G.make_batch(ctx, ticks)
     assert name in (f"tick_yuv_wave<{d}>", f"tick_general_yuv<{d}>"), name     # (strong downscales of 4-byte texels exceed the LDS budget)
     G.run_batch(ctx, h)
