@@ -82,19 +82,20 @@ static int parse_switch(const char *name, const char *value, int *out) {
     if (n == "CHV_WAVE_DMA") { *out = v == "0" ? 0 : 1; return 8; }
     if (n == "CHV_PASS_FUSE") { *out = v == "0" ? 0 : 1; return 9; }
     if (n == "CHV_GEOM_CACHE") { *out = v == "0" ? 0 : v == "eager" ? 2 : 1; return 10; }
+    if (n == "CHV_STREAM_ROWS") { const int r = atoi(v.c_str()); *out = (r >= 1 && r <= 4096) ? r : 0; return 11; }
     return -1;
 }
 static void store_switch(Switches &s, int which, int val) {
-    std::atomic<int> *slots[11] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
-                                    &s.pass_fuse, &s.geom_cache };
+    std::atomic<int> *slots[12] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
+                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows };
     slots[which]->store(val, std::memory_order_relaxed);
 }
 Switches &chv::switches() {
     static Switches s;
     static std::once_flag once;
     std::call_once(once, [] {
-        static const char *const names[11] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
-                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE" };
+        static const char *const names[12] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
+                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS" };
         for (const char *n : names) {
             const char *v = getenv(n);
             int val = 0, which = v ? parse_switch(n, v, &val) : -1;

@@ -95,6 +95,31 @@ CHV_DEV void st_store(uint8_t *row, uint32_t off, uint32_t v) {
     asm volatile("global_store_dword %0, %1, %2" :: "v"(off), "v"(v), "s"(row) : "memory");
 }
 
+// A layer's twelve tap bytes, read as ONE group and awaited ONCE: left to hipcc every tap is a byte read followed four instructions later
+// by an `s_waitcnt lgkmcnt(n)` of its own (45 waits per row at four layers, a wave asleep for an LDS round trip a dozen times per row).
+// The reads are issued by hand — hipcc neither counts them nor knows that their destinations are still being written — so the wait
+// statement names every destination as "+v": no consumer can be scheduled above it, and tests/test_stream_row_control_contract.py checks on
+// the built code that nothing touches a destination between its read and the wait that covers it.  LDS operations of a wave complete in
+// order and nothing but LDS reads counts in lgkmcnt inside the row loop (the refill's scalar loads are awaited there): `lgkmcnt(12)` with the
+// NEXT layer's group issued behind this one's means "this layer's twelve have arrived".
+struct StTaps { uint32_t y00, y10, y01, y11, u00, u10, u01, u11, v00, v10, v01, v11; };
+template <int LO, int LC, int LV>
+CHV_DEV void st_taps_read(StTaps &t, uint32_t aY00, uint32_t aY10, uint32_t aY01, uint32_t aY11, uint32_t aC00, uint32_t aC10, uint32_t aC01, uint32_t aC11) {
+    asm volatile("ds_read_u8 %0, %12 offset:%20\n\tds_read_u8 %1, %13 offset:%20\n\tds_read_u8 %2, %14 offset:%20\n\tds_read_u8 %3, %15 offset:%20\n\t"
+                 "ds_read_u8 %4, %16 offset:%21\n\tds_read_u8 %5, %17 offset:%21\n\tds_read_u8 %6, %18 offset:%21\n\tds_read_u8 %7, %19 offset:%21\n\t"
+                 "ds_read_u8 %8, %16 offset:%22\n\tds_read_u8 %9, %17 offset:%22\n\tds_read_u8 %10, %18 offset:%22\n\tds_read_u8 %11, %19 offset:%22"
+                 : "=&v"(t.y00), "=&v"(t.y10), "=&v"(t.y01), "=&v"(t.y11), "=&v"(t.u00), "=&v"(t.u10), "=&v"(t.u01), "=&v"(t.u11),
+                   "=&v"(t.v00), "=&v"(t.v10), "=&v"(t.v01), "=&v"(t.v11)
+                 : "v"(aY00), "v"(aY10), "v"(aY01), "v"(aY11), "v"(aC00), "v"(aC10), "v"(aC01), "v"(aC11), "n"(LO), "n"(LC), "n"(LV));
+}
+// wait until at most YOUNGER LDS reads issued after the group are outstanding: the group has arrived
+template <int YOUNGER>
+CHV_DEV void st_taps_wait(StTaps &t) {
+    asm volatile("s_waitcnt lgkmcnt(%12)"
+                 : "+v"(t.y00), "+v"(t.y10), "+v"(t.y01), "+v"(t.y11), "+v"(t.u00), "+v"(t.u10), "+v"(t.u01), "+v"(t.u11), "+v"(t.v00), "+v"(t.v10), "+v"(t.v01), "+v"(t.v11)
+                 : "n"(YOUNGER));
+}
+
 // ONE: a launch of one tick whose descriptors are kernel ARGUMENTS (tick_bgra_stream_one below) — `ticks` / `layers` point into the kernarg
 // segment, every field is a scalar load at a constant offset from one base, issued together: no tick -> first_layer -> layer chain of
 // dependent loads in front of a lone tick's waves, and no descriptor copy in front of the launch.
@@ -303,19 +328,37 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
         auto yoff = [&](int q) { return ((q >> 2) & 1) * (NL * ST_YL) + (q & 3) * ST_PITCH; };                       // layer 0's copy of luma row baseY + q
         auto coff = [&](int q) { return 2 * NL * ST_YL + ((q >> 1) & 1) * (NL * CLB) + (q & 1) * CPITCH; };
         const int sY0 = yoff(ry - baseY), sY1 = yoff(ry + 1 - baseY), sC0 = coff(rc - baseC), sC1 = coff(rc + 1 - baseC);
-        const uint8_t *pY00 = lds + (oy0 + sY0), *pY10 = lds + (oy1 + sY0), *pY01 = lds + (oy0 + sY1), *pY11 = lds + (oy1 + sY1);
-        const uint8_t *pC00 = lds + (oc0v + sC0), *pC10 = lds + (oc1v + sC0), *pC01 = lds + (oc0v + sC1), *pC11 = lds + (oc1v + sC1);
+        // LDS byte addresses of layer 0's taps: the rings' address and the row's slot are added on the scalar unit, the lane's column once per tap
+        const uint32_t bY0 = lds0 + (uint32_t)sY0, bY1 = lds0 + (uint32_t)sY1, bC0 = lds0 + (uint32_t)sC0, bC1 = lds0 + (uint32_t)sC1;
+        const uint32_t aY00 = bY0 + (uint32_t)oy0, aY10 = bY0 + (uint32_t)oy1, aY01 = bY1 + (uint32_t)oy0, aY11 = bY1 + (uint32_t)oy1;
+        const uint32_t aC00 = bC0 + (uint32_t)oc0v, aC10 = bC0 + (uint32_t)oc1v, aC01 = bC1 + (uint32_t)oc0v, aC11 = bC1 + (uint32_t)oc1v;
         const float iyb = __uint_as_float(re.z), icb = __uint_as_float(re.w);
         const float w00 = iya * iyb, w10 = ya * iyb, w01 = iya * yb, w11 = ya * yb;
         const float c00 = ica * icb, c10 = ca * icb, c01 = ica * cbw, c11 = ca * cbw;
         float r0 = 0.f, r1 = 0.f, r2 = 0.f;                          // img_clear_bgra: (0, 0, 0, 1) — the canvas pixel as float codes
-#pragma unroll
-        for (int l = 0; l < ((CHV_ST_ABL & 4) ? 0 : NL); l++) {
-            constexpr int dummy = 0; (void)dummy;
-            const int lo = l * ST_YL, lc = l * CLB;
-            const float fy = cs_mix_h(w00, w10, w01, w11, tap_h(pY00 + lo), tap_h(pY10 + lo), tap_h(pY01 + lo), tap_h(pY11 + lo));
-            const float fu = cs_mix_h(c00, c10, c01, c11, tap_h(pC00 + lc), tap_h(pC10 + lc), tap_h(pC01 + lc), tap_h(pC11 + lc));
-            const float fv = cs_mix_h(c00, c10, c01, c11, tap_h(pC00 + lc + VOFF), tap_h(pC10 + lc + VOFF), tap_h(pC01 + lc + VOFF), tap_h(pC11 + lc + VOFF));
+        // One wait per layer, and the next layer's taps in flight under this layer's arithmetic (a group belongs to the CURRENT row: nothing is
+        // read across rows, so the `s_waitcnt lgkmcnt(0)` in front of a ring request still means "the rows being overwritten have been read")
+        // (planar sources keep three more plane pointers per layer set and the V offsets: the twelve registers of a second group do not fit
+        // 80 there without scratch — each layer's group is read and awaited on its own, still one wait per layer)
+        constexpr bool AHEAD = !PL;
+        StTaps taps[2];
+        auto read_layer = [&](auto lt) {
+            constexpr int l = decltype(lt)::value;
+            st_taps_read<l * ST_YL, l * CLB, l * CLB + VOFF>(taps[l & 1], aY00, aY10, aY01, aY11, aC00, aC10, aC01, aC11);
+        };
+        if (!(CHV_ST_ABL & 4)) read_layer(std::integral_constant<int, 0>{});
+        auto layer = [&](auto lt) {
+            constexpr int l = decltype(lt)::value;
+            if constexpr (l < NL && !(CHV_ST_ABL & 4)) {
+            if constexpr (l + 1 < NL && AHEAD) { read_layer(std::integral_constant<int, l + 1>{}); st_taps_wait<12>(taps[l & 1]); }
+            else {
+                if constexpr (l > 0 && !AHEAD) read_layer(lt);
+                st_taps_wait<0>(taps[l & 1]);
+            }
+            const StTaps &t = taps[l & 1];
+            const float fy = cs_mix_h(w00, w10, w01, w11, tap_h(t.y00), tap_h(t.y10), tap_h(t.y01), tap_h(t.y11));
+            const float fu = cs_mix_h(c00, c10, c01, c11, tap_h(t.u00), tap_h(t.u10), tap_h(t.u01), tap_h(t.u11));
+            const float fv = cs_mix_h(c00, c10, c01, c11, tap_h(t.v00), tap_h(t.v10), tap_h(t.v01), tap_h(t.v11));
             if constexpr (ABS && CHV_STREAM_PMIX) {
                 // the layer's pixel enters the blend as a binary16 read from the high half of its clamped 16.16 sum (code x 2^-24, exact;
                 // the opacity carries the 2^24): p * a + inner in one v_fma_mix_f32, the same real numbers into the same single rounding
@@ -330,7 +373,7 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
                     r2 = __builtin_fmaf(a24, (float)code_h(cr), __builtin_fmaf(r2, ial[l], nrb[l]));
                 }
                 if (l + 1 < NL) { r0 += kRintBias; r1 += kRintBias; r2 += kRintBias; }
-                continue;
+                return;
             }
             float pb, pg, pr;
             if constexpr (ABS) yuv_to_bgr_floats_absorbed(csc[l], fy, fu, fv, pb, pg, pr);
@@ -343,7 +386,9 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
                 r2 = __builtin_fmaf(pr, al[l], __builtin_fmaf(r2, ial[l], nrb[l]));
             }
             if (l + 1 < NL) { r0 += kRintBias; r1 += kRintBias; r2 += kRintBias; }
-        }
+            }
+        };
+        layer(std::integral_constant<int, 0>{}); layer(std::integral_constant<int, 1>{}); layer(std::integral_constant<int, 2>{}); layer(std::integral_constant<int, 3>{});
         // (pack_codes with the alpha word as a separate source: tied to the destination it is re-materialised every row)
         uint32_t out;
         asm("v_cvt_pk_u8_f32 %0, %1, 0, %2" : "=v"(out) : "v"(r0), "v"(alpha_word));
@@ -446,6 +491,7 @@ hipError_t launch_bgra_stream(const DTick *ticks_host, const DLayer *layers_host
     const long rows_small = std::min<long>(CHV_STREAM_SMALL_ROWS_MAX, std::max<long>(CHV_STREAM_MIN_ROWS, (wave_rows + CHV_STREAM_SMALL_WAVES - 1) / CHV_STREAM_SMALL_WAVES));
     int rows = (int)std::max<long>(rows_small, (maxH + chunks - 1) / chunks);
     if (CHV_STREAM_ROWS_FIXED > 0) rows = CHV_STREAM_ROWS_FIXED;      // (sweeps: tools/build_variant.sh ... -DCHV_STREAM_ROWS_FIXED=n)
+    if (const int forced = switches().stream_rows.load(std::memory_order_relaxed)) rows = forced;      // (tests: CHV_STREAM_ROWS)
     rows = std::max(1, std::min(rows, maxH));
     const int chunks_y = (maxH + rows - 1) / rows;
     const long total = (long)n_ticks * chunks_y * ((strips_x + ST_WAVES - 1) / ST_WAVES);

@@ -2,7 +2,7 @@
 //
 // The environment is read ONCE, at the first use in the process (getenv on a hot path is undefined behaviour next to a
 // setenv in another thread, and the mixer and uploader threads run concurrently): CHV_FORCE_GENERAL, CHV_BGRA_PATH,
-// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
+// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
 // never through the environment.  Every value is an atomic int; 0 = "the library decides".
 #pragma once
 #include <atomic>
@@ -28,6 +28,8 @@ struct Switches {
                                          // batches mostly run once, so that its fuzzers reach the table-reading kernels)
     std::atomic<int> pass_fuse{1};       // CHV_PASS_FUSE: 1 (default) picture kernels issued inside chv_pass_begin ... chv_pass_end are held and leave as the one
                                          // fused launch chv_composite would make of them (chipvideo.cpp: PendingPass); 0 every chv_run_kernel launches at once
+    std::atomic<int> stream_rows{0};     // CHV_STREAM_ROWS: 1 .. 4096 canvas rows per chunk of tick_bgra_stream (tests: small launches take chunks of 4 .. 12 rows,
+                                         // and the kernel's row table is refilled every 32); 0 (default) launch_bgra_stream decides
 };
 Switches &switches();                    // (chipvideo.cpp; initialised from the environment on first use)
 
