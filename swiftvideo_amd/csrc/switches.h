@@ -2,7 +2,7 @@
 //
 // The environment is read ONCE, at the first use in the process (getenv on a hot path is undefined behaviour next to a
 // setenv in another thread, and the mixer and uploader threads run concurrently): CHV_FORCE_GENERAL, CHV_BGRA_PATH,
-// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
+// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
 // never through the environment.  Every value is an atomic int; 0 = "the library decides".
 #pragma once
 #include <atomic>
@@ -30,7 +30,16 @@ struct Switches {
                                          // fused launch chv_composite would make of them (chipvideo.cpp: PendingPass); 0 every chv_run_kernel launches at once
     std::atomic<int> stream_rows{0};     // CHV_STREAM_ROWS: 1 .. 4096 canvas rows per chunk of tick_bgra_stream (tests: small launches take chunks of 4 .. 12 rows,
                                          // and the kernel's row table is refilled every 32); 0 (default) launch_bgra_stream decides
+    std::atomic<int> stream_opaque{1};   // CHV_STREAM_OPAQUE: 0 launches whose bottom layers are all opaque keep tick_bgra_stream's general kernels (A/B and
+                                         // parity tests); 1 (default) they take the opaque-bottom kernels (kernels_stream_opq.hip.cpp)
 };
 Switches &switches();                    // (chipvideo.cpp; initialised from the environment on first use)
+
+// Counters the launchers keep for tests and probes (chv_debug_get_counter; process-wide, relaxed).  Defined in chipvideo.cpp: the host units
+// link without the kernel units (tests/stubhip), so the kernel units count here instead of exporting a reader.
+struct DebugCounters {
+    std::atomic<unsigned long long> stream_opaque_launches{0};       // launches of tick_bgra_stream that took the opaque-bottom kernels
+};
+DebugCounters &debug_counters();
 
 }  // namespace chv
