@@ -64,7 +64,7 @@ const char *chv_build_flags(void);
 /* Measurement / test hook: path-selection switches.  Names and values are those of the environment variables read once at
  * first use (CHV_FORCE_GENERAL=1, CHV_BGRA_PATH=wave|tiled|stream, CHV_WAVE_ROWS=8|16, CHV_TILE_ROWS=16|32, CHV_SAME_GEOM=0,
  * CHV_DESC=host|device, CHV_STREAM=0, CHV_YUV_STREAM=0|force, CHV_WAVE_DMA=0, CHV_PASS_FUSE=0, CHV_GEOM_CACHE=0|eager, CHV_STREAM_ROWS=n,
- * CHV_STREAM_OPAQUE=0);
+ * CHV_STREAM_OPAQUE=0, CHV_REBIND=scatter|copy);
  * NULL or "" restores the default.  Process-wide, atomic; not part of the Swift-facing contract. */
 int chv_debug_set_switch(const char *name, const char *value);
 /* Measurement / test hook: counters of the current device's store of strip-kernel geometry tables (csrc/geom_cache.h): "geom_store_patched"
@@ -319,8 +319,8 @@ int chv_composite(chv_context *ctx, const chv_image *target, int clear_first,
 
 /* Many independent ticks (streams / frames) in one launch: job i composites
  * layers[first_layer[i] .. first_layer[i]+n_layers[i]) onto targets[i].
- * A batch is immutable once created and can be run any number of times
- * (canvas and upload rings make the same descriptors recur every tick). */
+ * A batch can be run any number of times; its scene (kernels, uniforms, geometry) is fixed at
+ * creation, the pictures it is bound to can be exchanged with chv_batch_rebind below. */
 typedef struct chv_batch chv_batch;
 typedef struct chv_tick {
     chv_image target;
@@ -331,6 +331,34 @@ typedef struct chv_tick {
 int chv_batch_create(chv_context *ctx, const chv_tick *ticks, int n_ticks, chv_batch **out);
 int chv_batch_run(chv_context *ctx, chv_batch *batch);
 int chv_batch_destroy(chv_batch *batch);
+/* Point an existing batch at new pictures.  No reference counterpart: the reference issues every tick's kernels afresh.  What makes it worth
+ * having is that a real host never shows the same pictures twice — the upload ring and VideoMixer.getBacking's ring of 10 canvases
+ * (mix.video.swift:148-165) rotate every tick — while between two ticks of a scene nothing but plane addresses changes: rebinding and running
+ * replaces chv_batch_create + run + destroy per group tick.
+ *  - Same geometry, new memory.  A replacement must equal the picture it replaces in format, image size and plane count and, per used
+ *    plane, in width, height, components AND pitch (the route, LF_SAME_GEOM and the launch geometry were derived from them); on every route but
+ *    the general kernels its plane addresses must have the alignment the replaced ones had (modulo 16: multiples of 16 stay multiples of 16),
+ *    4-component planes need 4 everywhere.  Every check chv_batch_create makes of a plane applies (buffer valid and on the batch's device,
+ *    extent inside the buffer).  Anything else is CHV_ERR_INVALID_VALUE — or the BAD_INPUT / BAD_TARGET chv_batch_create gives for that plane —
+ *    and the detail text says to rebuild the batch.  Views at any offset inside larger parents are fine as long as these hold.
+ *  - All or nothing.  Every item is validated before anything changes; after an error (a failed enqueue included) the batch runs exactly as
+ *    before the call.  The same slot named twice in one call is CHV_ERR_INVALID_VALUE.
+ *  - Stream-ordered on ctx's stream like a run (a held pass goes out first): runs issued before the call composite the old pictures, runs
+ *    issued after it, from any context of the device, the new ones; no host wait is needed between rebind, run, rebind, run, and in the steady
+ *    state rebind -> run -> chv_pass_end(wait) the call never blocks the host.
+ *  - Dependencies follow the pictures: later runs wait for pending asynchronous uploads of the buffers bound NOW and never touch a buffer that
+ *    was rebound away, which may be freed once the runs issued before the rebind have completed.
+ *  - chv_batch_describe, the route, a split into two launches and the geometry tables are untouched.  Changing uniforms, opacity or geometry
+ *    is a new batch.
+ * CHV_REBIND=scatter|copy picks the mechanism (a small kernel that stores the new addresses / the whole descriptor block again); default: the
+ * library decides. */
+typedef struct chv_rebind {
+    int32_t tick;     /* index of the tick as given to chv_batch_create */
+    int32_t layer;    /* -1: the tick's target; 0..n_layers-1: that layer's image, position within the tick as given to
+                         chv_batch_create (also for batches that were split into two launches or have > 16 layers) */
+    chv_image image;  /* the picture that takes the slot's place */
+} chv_rebind;
+int chv_batch_rebind(chv_context *ctx, chv_batch *batch, const chv_rebind *items, int n_items);
 /* Name of the device kernel a batch dispatches to and its launch count (for profiling).  A batch whose ticks start with 2..4
  * full-frame videos of one geometry and go on with other layers runs as TWO launches on the context's stream ("tick_bgra_stream +
  * tick_bgra_wave": the videos, then the rest continuing on the canvas); the bytes are those of one pass. */

@@ -12,9 +12,10 @@
    host wait.  Current figures: INTEGRATION.md section 1 and the `workloads` of the default bench.py line (round 3: 256
    ticks per launch = 4.9 us of device time per tick; one tick at a time 23-25 us fused, 54-56 us as the unchanged
    clear + 4 launches sequence: legs pipeline_per_tick / pipeline_reference_sequence).  The per-tick figure of a group does
-   not include building the TickBatch: VideoMixerGroup.flush below makes a new one every tick (a device allocation and a
-   descriptor copy, ~10 us); a group whose members and canvas rings recur should keep its batches, keyed by the
-   (canvas, sources) tuple, as swiftvideo_amd/compute.py::LanczosBatch does for resizes.
+   not include building the TickBatch: VideoMixerGroup.flush below makes a new one every tick unless the group was made with
+   `reuseBatches: true` — then it keeps one batch per canvas format with the signature of its scene and points it at every tick's
+   pictures (TickBatch.rebind -> chv_batch_rebind: the upload ring and the ring of 10 canvases, mix.video.swift:148-165, rotate
+   every tick, and nothing but plane addresses changes between two ticks of a scene); figures in profiles/batch_rebind_notes.md.
 */
 #if GPGPU_HIP
 import Foundation
@@ -41,7 +42,7 @@ public final class TickBatch {
     public let count: Int
     public private(set) var kernelName = ""
     private var handle: OpaquePointer?
-    private let retained: [PictureSample]
+    private var retained: [PictureSample]
 
     public init(_ context: ComputeContext, ticks: [MixTick]) throws {
         guard !ticks.isEmpty else {
@@ -88,6 +89,59 @@ public final class TickBatch {
         return context
     }
 
+    /// Point the batch at the pictures of `ticks` (chv_batch_rebind): the same scene — kernels, uniforms, plane sizes and pitches —
+    /// over other memory.  Anything else throws and leaves the batch as it was.  Ordered on the context's stream like `run`.
+    public func rebind(_ context: ComputeContext, ticks: [MixTick]) throws -> ComputeContext {
+        var items = [chv_rebind]()
+        var keep = [PictureSample]()
+        for (index, tick) in ticks.enumerated() {
+            guard let targetImage = tick.target.imageBuffer(), let targetDesc = describeImage(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            items.append(chv_rebind(tick: Int32(index), layer: -1, image: targetDesc))
+            keep.append(tick.target)
+            for (position, (sample, _, _)) in tick.layers.enumerated() {
+                guard let image = sample.imageBuffer(), let desc = describeImage(image, maxPlanes: 3) else {
+                    throw ComputeError.badInputData(description: "Bad input image")
+                }
+                items.append(chv_rebind(tick: Int32(index), layer: Int32(position), image: desc))
+                keep.append(sample)
+            }
+        }
+        try checkStatus(chv_batch_rebind(context.handle, handle, &items, Int32(items.count)))
+        retained = keep                       // (the pictures rebound away are released: the runs that read them were issued before)
+        return context
+    }
+
+    /// What a batch is built from with the pictures' addresses left out: per tick the kernel ids, the 236 uniform bytes, clear_first,
+    /// and per picture its format, plane sizes, pitches and components.  Equal signatures: `rebind`; anything else: a new batch.
+    public static func sceneSignature(_ ticks: [MixTick]) throws -> Data {
+        var signature = Data()
+        func append<T>(_ value: T) {
+            var v = value
+            withUnsafeBytes(of: &v) { signature.append(contentsOf: $0) }
+        }
+        func picture(_ sample: PictureSample) throws {
+            guard let image = sample.imageBuffer(), let desc = describeImage(image, maxPlanes: 3) else {
+                throw ComputeError.badInputData(description: "Bad input image")
+            }
+            append(desc.format); append(desc.width); append(desc.height); append(desc.n_planes)
+            for plane in [desc.planes.0, desc.planes.1, desc.planes.2] {
+                append(plane.width); append(plane.height); append(plane.pitch); append(plane.components)
+            }
+        }
+        for tick in ticks {
+            try picture(tick.target)
+            append(tick.clearFirst); append(Int32(tick.layers.count))
+            for (sample, kernel, uniforms) in tick.layers {
+                let layer = try makeLayer(sample, kernel, uniforms)
+                append(layer.kernel); append(layer.uniforms); append(layer.opts.colorspace)
+                try picture(sample)
+            }
+        }
+        return signature
+    }
+
     deinit {
         if let batch = handle {
             _ = chv_batch_destroy(batch)      // safe from any thread; selects the device itself
@@ -101,10 +155,13 @@ public final class TickBatch {
 /// group composes all ticks submitted for one clock time with one launch per canvas format and one host wait, then
 /// runs every member's completion (which emits the member's PictureSample exactly as the unchanged code does).
 public final class VideoMixerGroup {
-    public init(_ context: ComputeContext, members: Int, flushAfter: DispatchTimeInterval = .milliseconds(2)) {
+    /// `reuseBatches`: keep one batch per canvas format with its scene signature; a tick of the same signature rebinds every picture and
+    /// runs, any difference — or a refused rebind — builds afresh.  Same bytes either way; off by default.
+    public init(_ context: ComputeContext, members: Int, flushAfter: DispatchTimeInterval = .milliseconds(2), reuseBatches: Bool = false) {
         self.context = createComputeContext(sharing: context)
         self.members = members
         self.flushAfter = flushAfter
+        self.reuseBatches = reuseBatches
         self.queue = DispatchQueue(label: "mix.video.group")
     }
 
@@ -138,7 +195,7 @@ public final class VideoMixerGroup {
             for (tick, _) in ticks {
                 byFormat[String(describing: tick.target.pixelFormat()), default: []].append(tick)
             }
-            let batches = try byFormat.values.map { try TickBatch(ctx, ticks: $0) }
+            let batches = try byFormat.map { try reuseBatches ? batch(ctx, format: $0.key, ticks: $0.value) : TickBatch(ctx, ticks: $0.value) }
             context = try usingContext(ctx) { try batches.reduce($0) { try $1.run($0) } }
         } catch let error {
             failure = error
@@ -146,13 +203,32 @@ public final class VideoMixerGroup {
         ticks.forEach { $0.1(failure) }
     }
 
+    /// the kept batch of this canvas format pointed at `ticks`, or a new one (kept in its place)
+    private func batch(_ ctx: ComputeContext, format: String, ticks: [MixTick]) throws -> TickBatch {
+        let signature = try TickBatch.sceneSignature(ticks)
+        if let (keptSignature, keptBatch) = kept[format], keptSignature == signature {
+            do {
+                _ = try keptBatch.rebind(ctx, ticks: ticks)
+                return keptBatch
+            } catch {
+                // (say, a picture at an address of another alignment: a new batch takes whatever it is given)
+            }
+        }
+        let fresh = try TickBatch(ctx, ticks: ticks)
+        kept[format] = (signature, fresh)
+        return fresh
+    }
+
     deinit {
+        kept.removeAll()
         if let ctx = context {
             try? destroyComputeContext(ctx)
         }
     }
 
     private var context: ComputeContext?
+    private let reuseBatches: Bool
+    private var kept = [String: (Data, TickBatch)]()
     private let members: Int
     private let flushAfter: DispatchTimeInterval
     private let queue: DispatchQueue

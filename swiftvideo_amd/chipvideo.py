@@ -79,6 +79,10 @@ class Tick(C.Structure):
                 ("layers", C.POINTER(Layer))]
 
 
+class Rebind(C.Structure):          # chv_rebind: one picture slot of a batch and the picture that takes its place
+    _fields_ = [("tick", C.c_int32), ("layer", C.c_int32), ("image", Image)]
+
+
 class SndUniforms(C.Structure):      # BufferUniforms, kernels.cl.swift:536-541
     _fields_ = [("input_count", C.c_int32), ("input_offsets", C.c_int32 * 8), ("input_gains", C.c_float * 8), ("input_fade", C.c_float * 8)]
 
@@ -124,6 +128,7 @@ _SIGNATURES = {
     "chv_batch_create": (C.c_int, [C.c_void_p, C.POINTER(Tick), C.c_int, C.POINTER(C.c_void_p)]),
     "chv_batch_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "chv_batch_destroy": (C.c_int, [C.c_void_p]),
+    "chv_batch_rebind": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Rebind), C.c_int]),
     "chv_batch_describe": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_int)]),
     "chv_scale_lanczos": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image)]),
     "chv_scale_lanczos_batch": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.c_int]),

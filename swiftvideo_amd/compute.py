@@ -627,7 +627,8 @@ class TickBatch:
     """Many independent mixer ticks issued as ONE launch (chv_batch_*): what a host with several mixers / streams on a
     device (composer.swift:203-224) uses instead of one chv_composite per tick.  Byte-identical to running the ticks
     one by one.  ticks: [(target PictureSample, clearFirst, [(kernel, PictureSample, uniforms, colorspace)])].
-    The batch keeps the descriptors on the device; the pictures it refers to must stay alive until it is destroyed."""
+    The batch keeps the descriptors on the device; the pictures it refers to must stay alive until it is destroyed or they
+    are rebound away (`rebind`) and the runs issued before that have completed."""
 
     def __init__(self, ctx, ticks):
         lib = cv.load()
@@ -655,9 +656,29 @@ class TickBatch:
         cv.check(cv.load().chv_batch_run(ctx.handle, self._h))
         return ctx
 
+    def rebind(self, ctx, items):
+        """Point slots of the batch at new pictures (chv_batch_rebind): items = [(tick, layer, PictureSample)], layer -1 = the tick's target.
+        A replacement has the geometry (format, plane sizes, pitches) of the picture it replaces; anything else raises ComputeError and
+        leaves the batch as it was.  Ordered on ctx's stream like `run`."""
+        if not items:
+            return ctx
+        arr = (cv.Rebind * len(items))()
+        for i, (tick, layer, sample) in enumerate(items):
+            d = _image_desc(sample)
+            if d is None:
+                raise ComputeError(4 if layer < 0 else 5, "picture has no GPU image buffer")
+            arr[i].tick, arr[i].layer, arr[i].image = int(tick), int(layer), d
+        cv.check(cv.load().chv_batch_rebind(ctx.handle, self._h, arr, len(items)))
+        # (the pictures bound now stay alive with the batch; those rebound away are the caller's again)
+        self._bound = getattr(self, "_bound", {})
+        for tick, layer, sample in items:
+            self._bound[(int(tick), int(layer))] = sample
+        return ctx
+
     def destroy(self):
         if self._h:
             cv.check(cv.load().chv_batch_destroy(self._h))
+            self._bound = {}
             self._h = C.c_void_p()
             self._keep = []
 
@@ -818,11 +839,62 @@ class VideoMixerGroup:
     (TickBatch) and one host wait, instead of one launch and one host wait per mixer (mix.video.swift:116-124 per mixer).  Each mixer keeps its own samples,
     backing ring and z-order; the result of `mix(at)` is the list of what every mixer's own `mix(at)` would return."""
 
-    def __init__(self, mixers):
+    def __init__(self, mixers, reuseBatches=False):
+        """reuseBatches: keep one batch per canvas format together with the signature of its scene; a group tick whose signature equals the
+        kept one rebinds every picture (TickBatch.rebind) and runs instead of building a batch, any difference (or a refused rebind) builds
+        afresh.  Same bytes either way."""
         if not mixers:
             raise ComputeError(0, "empty mixer group")
         self.mixers = list(mixers)
         self.context = self.mixers[0].clContext
+        self.reuseBatches = reuseBatches
+        self._kept = {}                 # canvas format -> (scene signature, TickBatch)
+        self.rebinds = self.rebuilds = 0
+
+    @staticmethod
+    def _picture_signature(sample):
+        d = _image_desc(sample)
+        if d is None:
+            return None
+        return (d.format, d.width, d.height, d.n_planes) + tuple((p.width, p.height, p.pitch, p.components) for p in d.planes[:max(0, min(3, d.n_planes))])
+
+    @classmethod
+    def _scene_signature(cls, group):
+        """what a batch is built from, the pictures' addresses left out: per tick the kernel ids, the 236 uniform bytes, the colourspace,
+        clear_first, and per picture its format, plane sizes, pitches and components"""
+        sig = []
+        for target, clear, layers in group:
+            sig.append((cls._picture_signature(target), bool(clear),
+                        tuple((int(k), _uniform_blob(u).tobytes(), int(csc), cls._picture_signature(im)) for k, im, u, csc in layers)))
+        return tuple(sig)
+
+    def _batch_for(self, fmt, group):
+        """the kept batch of this canvas format rebound to the group's pictures, or a new one (which is kept in its place)"""
+        sig = self._scene_signature(group)
+        kept = self._kept.get(fmt)
+        if kept is not None and kept[0] == sig:
+            items = []
+            for t, (target, _, layers) in enumerate(group):
+                items.append((t, -1, target))
+                items += [(t, l, layer[1]) for l, layer in enumerate(layers)]
+            try:
+                kept[1].rebind(self.context, items)
+                self.rebinds += 1
+                return kept[1]
+            except ComputeError:
+                pass                    # (say, a picture at an address of another alignment: a new batch takes whatever it is given)
+        if kept is not None:
+            kept[1].destroy()
+            del self._kept[fmt]
+        batch = TickBatch(self.context, group)
+        self._kept[fmt] = (sig, batch)
+        self.rebuilds += 1
+        return batch
+
+    def destroy(self):
+        for _, batch in self._kept.values():
+            batch.destroy()
+        self._kept = {}
 
     def mix(self, at=0.0):
         ticks, backings = [], []
@@ -839,7 +911,10 @@ class VideoMixerGroup:
             by_format = {}
             for tick in ticks:
                 by_format.setdefault(int(tick[0].pixelFormat()), []).append(tick)
-            batches = [TickBatch(self.context, group) for group in by_format.values()]
+            if self.reuseBatches:
+                batches = [self._batch_for(fmt, group) for fmt, group in by_format.items()]
+            else:
+                batches = [TickBatch(self.context, group) for group in by_format.values()]
             try:
                 def body(c):
                     for batch in batches:
@@ -847,8 +922,9 @@ class VideoMixerGroup:
                     return c
                 usingContext(self.context, body)
             finally:
-                for batch in batches:
-                    batch.destroy()
+                if not self.reuseBatches:
+                    for batch in batches:
+                        batch.destroy()
             out = [b.derive(pts=at, time=at, assetId=m.assetId()) for b, m in zip(backings, self.mixers)]
             for m in self.mixers:
                 m.result = ("nothing", None)

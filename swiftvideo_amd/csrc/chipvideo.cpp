@@ -25,6 +25,7 @@
 #include "device_types.h"
 #include "switches.h"
 #include "geom_cache.h"
+#include "rebind.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -84,19 +85,20 @@ static int parse_switch(const char *name, const char *value, int *out) {
     if (n == "CHV_GEOM_CACHE") { *out = v == "0" ? 0 : v == "eager" ? 2 : 1; return 10; }
     if (n == "CHV_STREAM_ROWS") { const int r = atoi(v.c_str()); *out = (r >= 1 && r <= 4096) ? r : 0; return 11; }
     if (n == "CHV_STREAM_OPAQUE") { *out = v == "0" ? 0 : 1; return 12; }
+    if (n == "CHV_REBIND") { *out = v == "scatter" ? 1 : v == "copy" ? 2 : 0; return 13; }
     return -1;
 }
 static void store_switch(Switches &s, int which, int val) {
-    std::atomic<int> *slots[13] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
-                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows, &s.stream_opaque };
+    std::atomic<int> *slots[14] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
+                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows, &s.stream_opaque, &s.rebind };
     slots[which]->store(val, std::memory_order_relaxed);
 }
 Switches &chv::switches() {
     static Switches s;
     static std::once_flag once;
     std::call_once(once, [] {
-        static const char *const names[13] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
-                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS", "CHV_STREAM_OPAQUE" };
+        static const char *const names[14] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
+                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS", "CHV_STREAM_OPAQUE", "CHV_REBIND" };
         for (const char *n : names) {
             const char *v = getenv(n);
             int val = 0, which = v ? parse_switch(n, v, &val) : -1;
@@ -105,6 +107,9 @@ Switches &chv::switches() {
     });
     return s;
 }
+// the scatter kernel's launcher (rebind.h): null until kernels_rebind.hip.cpp registers it, and for good in a build without that unit
+static std::atomic<RebindLauncher> g_rebind_launcher{nullptr};
+void chv::register_rebind_launcher(RebindLauncher fn) { g_rebind_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -133,7 +138,8 @@ extern "C" const char *chv_build_flags(void) {
     // another major version until tools/check_inflight.py and the GPU suite have been re-run with it), every timing-only ablation macro
     static const std::string flags = std::string("arch=" CHV_ARCH ";hipcc=" CHV_HIPCC_VERSION ";clang=") + std::to_string(__clang_major__) + "." + std::to_string(__clang_minor__) +
                                      ";fp_contract=off;" + bgra_wave_build_flags() + ";" + yuv_wave_build_flags() + ";" + bgra_stream_build_flags() + ";" +
-                                     yuv_stream_build_flags() + ";" + lanczos_build_flags();
+                                     yuv_stream_build_flags() + ";" + lanczos_build_flags() +
+                                     (g_rebind_launcher.load(std::memory_order_acquire) ? ";batch_rebind:scatter=1" : ";batch_rebind:scatter=0");
     return flags.c_str();
 }
 
@@ -478,6 +484,22 @@ struct chv_batch {
     std::vector<DLayer> h_layers;
     std::string kernel_name;
     GeomCache geom;                // the strip kernels' per-layer geometry, computed once per launch configuration (geom_cache.h)
+    // ---- chv_batch_rebind: what a picture slot (a tick's target: slot t; a layer's image: slot n_ticks + its index in h_layers) was created with ----
+    struct SlotMeta { int32_t format, width, height, n_planes; };
+    std::vector<SlotMeta> slot_meta;
+    std::vector<chv_buffer *> slot_bufs;   // three per slot: the buffer behind every used plane (the descriptors hold raw addresses only) — `deps` follows them
+    std::vector<uint32_t> slot_stamp;      // the rebind call that named the slot last (a slot named twice in one call is an error)
+    uint32_t rebind_gen = 0;
+    size_t lo = 0, t2o = 0, used = 0;      // a pooled block's sections: layers at `lo`, the second launch's ticks at `t2o`, `used` bytes in all
+    // pinned lists of {offset, address} pairs for rebinds too long for kernel arguments, two of them in turn, and the event behind the last launch
+    // that read each (index 2: behind the last whole-block copy out of the block's pinned twin)
+    RebindItem *stage[2] = { nullptr, nullptr };
+    RebindItem *stage_dev[2] = { nullptr, nullptr };
+    size_t stage_cap[2] = { 0, 0 };
+    hipEvent_t stage_ev[3] = { nullptr, nullptr, nullptr };
+    bool stage_pending[3] = { false, false, false };
+    int next_stage = 0;
+    bool twin_rewritten = false;           // the twin has been refilled by a rebind (before that the copy that may still read it is the creation's: blk.ev)
 };
 
 static bool ctx_ok(chv_context *c) { return c && c->magic == 0x43485643 && c->stream; }
@@ -1639,6 +1661,7 @@ extern "C" int chv_batch_create(chv_context *c, const chv_tick *ticks, int n_tic
         if (e != hipSuccess) { desc_block_release(c->device, K); return hip_fail(e, "descriptors of a batch"); }
         K.recorded = true; K.last = c->stream;
         b->d_ticks = (DTick *)K.dev; b->d_layers = (DLayer *)(K.dev + lo); b->d_ticks2 = t2b ? (DTick *)(K.dev + t2o) : nullptr;
+        b->lo = lo; b->t2o = t2o; b->used = total;
     } else {
         e = hipMalloc((void **)&b->d_ticks, tb);
         if (e == hipSuccess) e = hipMalloc((void **)&b->d_layers, lb);
@@ -1656,6 +1679,25 @@ extern "C" int chv_batch_create(chv_context *c, const chv_tick *ticks, int n_tic
     b->h_ticks = std::move(dts);
     b->h_layers = std::move(dls);
     b->deps = deps.deps();
+    // what chv_batch_rebind compares a replacement with, and the buffer behind every plane (`deps` is recomputed from these after a rebind)
+    {
+        const size_t n_slots = (size_t)n_ticks + b->h_layers.size();
+        b->slot_meta.resize(n_slots);
+        b->slot_bufs.assign(n_slots * 3, nullptr);
+        b->slot_stamp.assign(n_slots, 0);
+        for (int i = 0; i < n_ticks; i++) {
+            const chv_image &T = ticks[i].target;
+            b->slot_meta[(size_t)i] = chv_batch::SlotMeta{ T.format, T.width, T.height, T.n_planes };
+            for (int p = 0; p < 3; p++) if (b->h_ticks[(size_t)i].dst.pl[p].ptr) b->slot_bufs[(size_t)i * 3 + p] = T.planes[p].buffer;
+            const size_t first = (size_t)b->h_ticks[(size_t)i].first_layer;
+            for (int l = 0; l < ticks[i].n_layers; l++) {
+                const chv_image &I = ticks[i].layers[l].image;
+                const size_t s = (size_t)n_ticks + first + (size_t)l;
+                b->slot_meta[s] = chv_batch::SlotMeta{ I.format, I.width, I.height, I.n_planes };
+                for (int p = 0; p < 3; p++) if (b->h_layers[first + (size_t)l].src.pl[p].ptr) b->slot_bufs[s * 3 + p] = I.planes[p].buffer;
+            }
+        }
+    }
     *out = b.release();
     return CHV_OK;
 }
@@ -1692,6 +1734,165 @@ extern "C" int chv_batch_run(chv_context *c, chv_batch *b) {
     return CHV_OK;
 }
 
+// Point slots of a batch at new pictures (chipvideo.h).  Nothing but DPlane::ptr fields changes: every item is checked against what its slot was
+// created with (same format, plane sizes, pitches, components; same address residue modulo 16 on the fast routes, which were chosen under
+// aligned16-style conditions), then the new addresses go to the device — by the scatter kernel (rebind.h) or as the whole block again —, ordered
+// on c's stream behind every earlier run of the batch, and only then the host copies, the per-slot buffers and `deps` follow.
+extern "C" int chv_batch_rebind(chv_context *c, chv_batch *b, const chv_rebind *items, int n_items) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (!b || !b->d_ticks) return fail(CHV_ERR_INVALID_VALUE, "bad batch");
+    if (n_items < 0 || (n_items > 0 && !items)) return fail(CHV_ERR_INVALID_VALUE, "null items");
+    if (b->device != c->device) return fail(CHV_ERR_INVALID_CONTEXT, "batch belongs to device %d", b->device);
+    if (n_items == 0) return CHV_OK;
+    const bool fast = b->fast_path >= 0 || b->fast_path2 >= 0;
+    const bool split = !b->h_ticks2.empty();
+    if (++b->rebind_gen == 0) { std::fill(b->slot_stamp.begin(), b->slot_stamp.end(), 0u); b->rebind_gen = 1; }
+    struct NewPlane { uint32_t slot; int32_t p; uint8_t *ptr; chv_buffer *buf; };
+    static thread_local std::vector<NewPlane> np;
+    static thread_local std::vector<RebindItem> list;
+    np.clear(); list.clear();
+    const size_t tick_plane = offsetof(DTick, dst) + offsetof(DImage, pl), layer_plane = offsetof(DLayer, src) + offsetof(DImage, pl);
+    // ---- every item is checked before anything changes
+    for (int k = 0; k < n_items; k++) {
+        const chv_rebind &it = items[k];
+        if (it.tick < 0 || it.tick >= b->n_ticks) return fail(CHV_ERR_INVALID_VALUE, "item %d: tick %d of %d", k, it.tick, b->n_ticks);
+        const DTick &T = b->h_ticks[(size_t)it.tick];
+        const int n_layers = T.n_layers + (split ? b->h_ticks2[(size_t)it.tick].n_layers : 0);
+        if (it.layer < -1 || it.layer >= n_layers) return fail(CHV_ERR_INVALID_VALUE, "item %d: layer %d of %d", k, it.layer, n_layers);
+        const bool target = it.layer < 0;
+        const size_t li = target ? 0 : (size_t)T.first_layer + (size_t)it.layer;
+        const size_t slot = target ? (size_t)it.tick : (size_t)b->n_ticks + li;
+        if (b->slot_stamp[slot] == b->rebind_gen) return fail(CHV_ERR_INVALID_VALUE, "item %d: tick %d, layer %d is named twice", k, it.tick, it.layer);
+        b->slot_stamp[slot] = b->rebind_gen;
+        const chv_batch::SlotMeta &M = b->slot_meta[slot];
+        const chv_image &I = it.image;
+        if (I.format != M.format || I.width != M.width || I.height != M.height || I.n_planes != M.n_planes)
+            return fail(CHV_ERR_INVALID_VALUE, "item %d: a %dx%d picture of format %d with %d planes cannot take the place of a %dx%d one of format %d with %d: rebuild the batch",
+                        k, I.width, I.height, I.format, I.n_planes, M.width, M.height, M.format, M.n_planes);
+        const DImage &old = target ? T.dst : b->h_layers[li].src;
+        for (int p = 0; p < 3; p++) {
+            const DPlane &O = old.pl[p];
+            if (!O.ptr) continue;
+            DPlane N;
+            int rc = plane_to_device(I.planes[p], O.comps, b->device, &N, target ? CHV_ERR_BAD_TARGET : CHV_ERR_BAD_INPUT, target ? "target" : "input", p);
+            if (rc) return rc;
+            if (N.w != O.w || N.h != O.h || N.pitch != O.pitch)
+                return fail(CHV_ERR_INVALID_VALUE, "item %d, plane %d: %dx%d with pitch %d cannot take the place of %dx%d with pitch %d: rebuild the batch",
+                            k, p, N.w, N.h, N.pitch, O.w, O.h, O.pitch);
+            if (fast && ((((uintptr_t)N.ptr) ^ ((uintptr_t)O.ptr)) & 15))
+                return fail(CHV_ERR_INVALID_VALUE, "item %d, plane %d: the batch's route (%s) was chosen for an address of another alignment: rebuild the batch",
+                            k, p, b->kernel_name.c_str());
+            np.push_back(NewPlane{ (uint32_t)slot, p, N.ptr, I.planes[p].buffer });
+            const size_t in_image = (size_t)p * sizeof(DPlane) + offsetof(DPlane, ptr);
+            if (target) {
+                list.push_back(RebindItem{ (uint32_t)((size_t)it.tick * sizeof(DTick) + tick_plane + in_image), 0, (uint64_t)(uintptr_t)N.ptr });
+                if (split) list.push_back(RebindItem{ (uint32_t)(b->t2o + (size_t)it.tick * sizeof(DTick) + tick_plane + in_image), 0, (uint64_t)(uintptr_t)N.ptr });
+            } else {
+                list.push_back(RebindItem{ (uint32_t)(b->lo + li * sizeof(DLayer) + layer_plane + in_image), 0, (uint64_t)(uintptr_t)N.ptr });
+            }
+        }
+    }
+    if (np.empty()) return CHV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // the host copies with the new addresses (h_ticks / h_layers / h_ticks2 carry the table words the launcher patched: geom_cache.h)
+    auto apply = [&](DTick *ht, DLayer *hl, DTick *ht2) {
+        for (const NewPlane &n : np) {
+            if (n.slot < (uint32_t)b->n_ticks) { ht[n.slot].dst.pl[n.p].ptr = n.ptr; if (ht2) ht2[n.slot].dst.pl[n.p].ptr = n.ptr; }
+            else hl[n.slot - (uint32_t)b->n_ticks].src.pl[n.p].ptr = n.ptr;
+        }
+    };
+    if (!b->blk.dev) {
+        // allocations of its own (the pool was full when the batch was made): no event orders them against runs on other streams — the device is
+        // drained, and the three arrays go again synchronously
+        std::vector<DTick> nt = b->h_ticks, nt2 = b->h_ticks2;
+        std::vector<DLayer> nl = b->h_layers;
+        apply(nt.data(), nl.data(), split ? nt2.data() : nullptr);
+        HIP_TRY(hipDeviceSynchronize());
+        hipError_t e = hipMemcpy(b->d_ticks, nt.data(), sizeof(DTick) * nt.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !nl.empty()) e = hipMemcpy(b->d_layers, nl.data(), sizeof(DLayer) * nl.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess && split) e = hipMemcpy(b->d_ticks2, nt2.data(), sizeof(DTick) * nt2.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            // put back what may have been overwritten: the batch runs as before the call
+            (void)hipGetLastError();
+            (void)hipMemcpy(b->d_ticks, b->h_ticks.data(), sizeof(DTick) * b->h_ticks.size(), hipMemcpyHostToDevice);
+            if (!b->h_layers.empty()) (void)hipMemcpy(b->d_layers, b->h_layers.data(), sizeof(DLayer) * b->h_layers.size(), hipMemcpyHostToDevice);
+            if (split) (void)hipMemcpy(b->d_ticks2, b->h_ticks2.data(), sizeof(DTick) * b->h_ticks2.size(), hipMemcpyHostToDevice);
+            (void)hipGetLastError();
+            return hip_fail(e, "descriptors of a batch (rebind)");
+        }
+    } else {
+        DescBlock &K = b->blk;
+        for (const RebindItem &r : list)
+            if ((r.off & 7) || (size_t)r.off + 8 > b->used) return fail(CHV_ERR_UNKNOWN, "rebind: offset %u outside the block's %zu bytes", r.off, b->used);
+        const RebindLauncher launcher = g_rebind_launcher.load(std::memory_order_acquire);
+        const int mode = switches().rebind.load(std::memory_order_relaxed);
+        const bool scatter = launcher && mode != 2;
+        // before a pinned area is overwritten: the last stream operation that read it (a host that waited for its tick never blocks here)
+        auto await_stage = [&](int i) -> hipError_t {
+            if (!b->stage_ev[i]) return hipEventCreateWithFlags(&b->stage_ev[i], hipEventDisableTiming);
+            if (!b->stage_pending[i]) return hipSuccess;
+            hipError_t e = hipEventSynchronize(b->stage_ev[i]);
+            if (e == hipSuccess) b->stage_pending[i] = false;
+            return e;
+        };
+        int si = -1;
+        hipError_t e = hipSuccess;
+        const RebindItem *list_dev = nullptr;
+        if (scatter && (int)list.size() > kRebindByValue) {
+            si = b->next_stage;
+            if ((e = await_stage(si)) != hipSuccess) return hip_fail(e, "rebind: waiting for the item list's last reader");
+            if (b->stage_cap[si] < list.size()) {
+                if (b->stage[si]) { (void)hipHostFree(b->stage[si]); b->stage[si] = nullptr; b->stage_dev[si] = nullptr; b->stage_cap[si] = 0; }
+                size_t cap = 1024;
+                while (cap < list.size()) cap <<= 1;
+                e = hipHostMalloc((void **)&b->stage[si], cap * sizeof(RebindItem), hipHostMallocMapped);
+                if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&b->stage_dev[si], b->stage[si], 0);
+                if (e != hipSuccess) { if (b->stage[si]) (void)hipHostFree(b->stage[si]); b->stage[si] = nullptr; return hip_fail(e, "rebind: pinned item list"); }
+                b->stage_cap[si] = cap;
+            }
+            memcpy(b->stage[si], list.data(), list.size() * sizeof(RebindItem));
+            list_dev = b->stage_dev[si];
+        } else if (!scatter) {
+            si = 2;
+            if ((e = await_stage(si)) != hipSuccess) return hip_fail(e, "rebind: waiting for the twin's last copy");
+            if (!b->twin_rewritten && K.recorded && (e = hipEventSynchronize(K.ev)) != hipSuccess) return hip_fail(e, "rebind: waiting for the twin's first copy");
+            memcpy(K.host, b->h_ticks.data(), sizeof(DTick) * b->h_ticks.size());
+            if (!b->h_layers.empty()) memcpy(K.host + b->lo, b->h_layers.data(), sizeof(DLayer) * b->h_layers.size());
+            if (split) memcpy(K.host + b->t2o, b->h_ticks2.data(), sizeof(DTick) * b->h_ticks2.size());
+            apply((DTick *)K.host, (DLayer *)(K.host + b->lo), split ? (DTick *)(K.host + b->t2o) : nullptr);
+            b->twin_rewritten = true;
+        }
+        // behind every run issued so far, on whatever stream (the block's event), and in front of every run to come
+        if (K.last != c->stream) HIP_TRY(hipStreamWaitEvent(c->stream, K.ev, 0));
+        if (scatter) e = launcher(K.dev, list.data(), list_dev, (int)list.size(), c->stream);
+        else e = hipMemcpyAsync(K.dev, K.host, b->used, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { (void)hipGetLastError(); return hip_fail(e, scatter ? "batch_rebind_scatter" : "descriptors of a batch (rebind)"); }
+        if (hipEventRecord(K.ev, c->stream) == hipSuccess) { K.last = c->stream; K.recorded = true; }
+        else {
+            // no marker behind the operation: nothing may overtake it
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(c->stream);
+        }
+        if (si >= 0) {
+            if (hipEventRecord(b->stage_ev[si], c->stream) == hipSuccess) b->stage_pending[si] = true;
+            else { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); }
+            if (si < 2) b->next_stage = si ^ 1;
+        }
+    }
+    // ---- the device has (or will have, in stream order) the new addresses: the host side follows
+    apply(b->h_ticks.data(), b->h_layers.data(), split ? b->h_ticks2.data() : nullptr);
+    for (const NewPlane &n : np) b->slot_bufs[(size_t)n.slot * 3 + (size_t)n.p] = n.buf;
+    // the buffers a run waits for are those bound NOW (one rebound away may be freed by its owner: it is not touched again)
+    {
+        DepScope scope;
+        scope.bufs.reserve(b->slot_bufs.size());
+        for (chv_buffer *q : b->slot_bufs) if (q) scope.bufs.push_back(q);
+        b->deps = scope.deps();
+    }
+    return CHV_OK;
+}
+
 extern "C" int chv_batch_destroy(chv_batch *b) {
     if (!b) return fail(CHV_ERR_INVALID_VALUE, "null batch");
     (void)hipSetDevice(b->device);
@@ -1702,6 +1903,11 @@ extern "C" int chv_batch_destroy(chv_batch *b) {
         if (b->d_ticks2) (void)hipFree(b->d_ticks2);
     }
     geom_cache_release(b->geom);
+    // (a rebind's launch may still be reading a pinned list: its event first)
+    for (int i = 0; i < 3; i++) {
+        if (b->stage_ev[i]) { if (b->stage_pending[i]) (void)hipEventSynchronize(b->stage_ev[i]); (void)hipEventDestroy(b->stage_ev[i]); }
+        if (i < 2 && b->stage[i]) (void)hipHostFree(b->stage[i]);
+    }
     b->d_ticks = nullptr;
     delete b;
     return CHV_OK;

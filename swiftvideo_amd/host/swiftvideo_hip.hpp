@@ -535,6 +535,53 @@ public:
     TickBatch(const TickBatch &) = delete;
     ~TickBatch() { if (batch_) chv_batch_destroy(batch_); }
     ComputeContext run(ComputeContext ctx) const { check(chv_batch_run(ctx.get(), batch_)); return ctx; }   // inside a compute pass
+    // Point the batch at the pictures of `ticks` (chv_batch_rebind): the same scene — kernels, uniforms, plane sizes and pitches — over other
+    // memory.  Anything else throws and leaves the batch as it was.  Ordered on ctx's stream like run().
+    ComputeContext rebind(ComputeContext ctx, const std::vector<Tick> &ticks) {
+        std::vector<chv_rebind> items;
+        for (size_t i = 0; i < ticks.size(); i++) {
+            chv_rebind r;
+            std::memset(&r, 0, sizeof r);
+            r.tick = (int32_t)i; r.layer = -1;
+            if (!describe(ticks[i].target, &r.image)) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+            items.push_back(r);
+            for (size_t l = 0; l < ticks[i].layers.size(); l++) {
+                r.layer = (int32_t)l;
+                if (!describe(ticks[i].layers[l].image, &r.image)) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+                items.push_back(r);
+            }
+        }
+        check(chv_batch_rebind(ctx.get(), batch_, items.data(), (int)items.size()));
+        keep_ = ticks;                             // (the pictures rebound away are the caller's again)
+        return ctx;
+    }
+    // what a batch is built from with the pictures' addresses left out: per tick the kernel ids, the 236 uniform bytes, the colourspace,
+    // clear_first, and per picture its format, plane sizes, pitches and components (VideoMixerGroup: equal signature = rebind, else rebuild)
+    static std::string sceneSignature(const std::vector<Tick> &ticks) {
+        std::string sig;
+        auto put = [&sig](const void *p, size_t n) { sig.append((const char *)p, n); };
+        auto picture = [&](const PictureSample &s) {
+            chv_image d;
+            std::memset(&d, 0, sizeof d);
+            const int32_t ok = describe(s, &d) ? 1 : 0;
+            put(&ok, sizeof ok);
+            const int32_t head[4] = { d.format, d.width, d.height, d.n_planes };
+            put(head, sizeof head);
+            for (int i = 0; i < 3; i++) { const int32_t pl[4] = { d.planes[i].width, d.planes[i].height, d.planes[i].pitch, d.planes[i].components }; put(pl, sizeof pl); }
+        };
+        for (const Tick &t : ticks) {
+            picture(t.target);
+            const int32_t head[2] = { t.clearFirst ? 1 : 0, (int32_t)t.layers.size() };
+            put(head, sizeof head);
+            for (const TickLayer &l : t.layers) {
+                const int32_t k[2] = { (int32_t)l.kernel, (int32_t)l.colorspace };
+                put(k, sizeof k);
+                put(&l.uniforms, sizeof l.uniforms);
+                picture(l.image);
+            }
+        }
+        return sig;
+    }
     std::string kernelName;
 private:
     chv_batch *batch_ = nullptr;
@@ -677,7 +724,10 @@ private:
 // launch and one wait per mixer; each element of the result is what that mixer's own mix(at) returns.
 class VideoMixerGroup {
 public:
-    explicit VideoMixerGroup(std::vector<VideoMixer *> mixers) : mixers_(std::move(mixers)) {}
+    // reuseBatches: keep one batch per canvas format with the signature of its scene (TickBatch::sceneSignature); a group tick of the same
+    // signature rebinds every picture and runs, any difference — or a refused rebind — builds afresh.  Same bytes either way.
+    explicit VideoMixerGroup(std::vector<VideoMixer *> mixers, bool reuseBatches = false) : mixers_(std::move(mixers)), reuse_(reuseBatches) {}
+    int rebinds = 0, rebuilds = 0;
     std::vector<EventBox<PictureSample>> mix(double at) {
         std::vector<EventBox<PictureSample>> out(mixers_.size());
         try {
@@ -688,9 +738,21 @@ public:
                 backings.push_back(t.target);
                 byFormat[(int)t.target.pixelFormat()].push_back(std::move(t));
             }
-            std::vector<std::unique_ptr<TickBatch>> batches;
-            for (auto &kv : byFormat) batches.emplace_back(new TickBatch(mixers_[0]->context(), kv.second));
-            usingContext(mixers_[0]->context(), [&](ComputeContext c) { for (auto &b : batches) c = b->run(c); return c; });
+            std::vector<std::unique_ptr<TickBatch>> fresh;
+            std::vector<TickBatch *> batches;
+            for (auto &kv : byFormat) {
+                if (!reuse_) { fresh.emplace_back(new TickBatch(mixers_[0]->context(), kv.second)); batches.push_back(fresh.back().get()); continue; }
+                Kept &k = kept_[kv.first];
+                const std::string sig = TickBatch::sceneSignature(kv.second);
+                bool rebound = false;
+                if (k.batch && k.signature == sig) {
+                    try { k.batch->rebind(mixers_[0]->context(), kv.second); rebound = true; rebinds++; }
+                    catch (const ComputeError &) {}          // (say, a picture at an address of another alignment: a new batch takes whatever it is given)
+                }
+                if (!rebound) { k.batch.reset(); k.batch.reset(new TickBatch(mixers_[0]->context(), kv.second)); k.signature = sig; rebuilds++; }
+                batches.push_back(k.batch.get());
+            }
+            usingContext(mixers_[0]->context(), [&](ComputeContext c) { for (TickBatch *b : batches) c = b->run(c); return c; });
             for (size_t i = 0; i < mixers_.size(); i++) {
                 out[i].kind = out[i].just; out[i].value = backings[i];
                 out[i].value.pts = at; out[i].value.time = at; out[i].value.assetId = mixers_[i]->assetId();
@@ -705,7 +767,10 @@ public:
         return out;
     }
 private:
+    struct Kept { std::string signature; std::unique_ptr<TickBatch> batch; };
     std::vector<VideoMixer *> mixers_;
+    bool reuse_ = false;
+    std::map<int, Kept> kept_;
 };
 
 // ---- PictureFilter: the Tx<PictureSample, PictureSample> the reference sketches and leaves commented out

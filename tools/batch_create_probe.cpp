@@ -2,7 +2,11 @@
 // builds the batch for that tick, runs it once and frees it — the real use: every tick has new pictures — against running one prebuilt batch again
 // (what bench.py times): chv_batch_create / chv_batch_run / chv_pass_end(wait) / chv_batch_destroy in microseconds, for groups of 8, 64 and 256
 // headline ticks (4 x 1080p NV12 -> 720p BGRA).  Native host over the C ABI.
+// --rebind: the third way, chv_batch_rebind — ONE batch kept and pointed at every group tick's pictures (rotating source and canvas rings), with
+// both mechanisms (CHV_REBIND=copy | scatter), against the prebuilt batch and the batch built fresh, alternating in one process; medians of 31
+// and the spread of the prebuilt batch's times (profiles/batch_rebind_notes.md).
 //   g++ -std=c++17 -O2 tools/batch_create_probe.cpp -Iinclude -Lswiftvideo_amd -lchipvideo -Wl,-rpath,$PWD/swiftvideo_amd -o tools/batch_create_probe.bin
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +19,7 @@ static double now() { return std::chrono::duration<double, std::micro>(std::chro
 int main(int argc, char **argv) {
     const bool json = argc > 1 && !strcmp(argv[1], "--json");          // (bench.py --full: the leg group_tick_built_fresh)
     const bool mixer = argc > 1 && !strcmp(argv[1], "--mixer");        // the reference-default mixer tick instead (1080p y420p canvas <- video + 2 BGRA overlays: strip kernel)
+    const bool rebind = argc > 1 && !strcmp(argv[1], "--rebind");      // chv_batch_rebind against the two ways above
     const int device = argc > 2 ? atoi(argv[2]) : 0;
     chv_context *ctx = nullptr;
     CK(chv_context_create(device, &ctx));
@@ -77,6 +82,69 @@ int main(int argc, char **argv) {
             for (int i = 0; i < 4; i++) uo[k].texture_transform[5 * i] = 1.f;
             uo[k].input_size[0] = 640; uo[k].input_size[1] = 360; uo[k].output_size[0] = 1920; uo[k].output_size[1] = 1080; uo[k].opacity = k ? .6f : .8f;
         }
+    }
+    if (rebind) {
+        auto median = [](std::vector<double> v) { std::sort(v.begin(), v.end()); return v[v.size() / 2]; };
+        printf("{");
+        bool first = true;
+        for (int G : { 8, 64, 256 }) {
+            std::vector<chv_layer> layers((size_t)G * LAYERS);
+            std::vector<chv_tick> ticks(G);
+            std::vector<chv_rebind> items((size_t)G * (1 + LAYERS));
+            // the pictures of group tick `it`: as batch descriptors and as a rebind list
+            auto pictures = [&](int it) {
+                for (int t = 0; t < G; t++) {
+                    for (int l = 0; l < LAYERS; l++) {
+                        chv_layer &L = layers[(size_t)t * LAYERS + l];
+                        memset(&L, 0, sizeof L);
+                        L.kernel = CHV_K_IMG_NV12_BGRA; L.image = simg[(t + l + it) % NSRC]; L.uniforms = u; L.uniforms.opacity = op[l]; L.opts = opts;
+                        items[(size_t)t * (1 + LAYERS) + 1 + l] = chv_rebind{ t, l, L.image };
+                    }
+                    memset(&ticks[t], 0, sizeof(chv_tick));
+                    ticks[t].target = cimg[(t + it) % NCAN]; ticks[t].clear_first = 1; ticks[t].n_layers = LAYERS; ticks[t].layers = &layers[(size_t)t * LAYERS];
+                    items[(size_t)t * (1 + LAYERS)] = chv_rebind{ t, -1, ticks[t].target };
+                }
+            };
+            pictures(0);
+            chv_batch *prebuilt = nullptr, *kept = nullptr;
+            CK(chv_batch_create(ctx, ticks.data(), G, &prebuilt));
+            CK(chv_batch_create(ctx, ticks.data(), G, &kept));
+            std::vector<double> ta, tb, tc, td, tc_call, td_call;
+            const int N = 31, WARM = 5;
+            for (int it = 1; it <= N + WARM; it++) {
+                pictures(it);
+                double t0 = now();
+                CK(chv_batch_run(ctx, prebuilt)); CK(chv_pass_end(ctx, 1));
+                double t1 = now();
+                chv_batch *b = nullptr;
+                CK(chv_batch_create(ctx, ticks.data(), G, &b)); CK(chv_batch_run(ctx, b)); CK(chv_pass_end(ctx, 1)); CK(chv_batch_destroy(b));
+                double t2 = now();
+                CK(chv_debug_set_switch("CHV_REBIND", "copy"));
+                double t3 = now();
+                CK(chv_batch_rebind(ctx, kept, items.data(), (int)items.size()));
+                double t4 = now();
+                CK(chv_batch_run(ctx, kept)); CK(chv_pass_end(ctx, 1));
+                double t5 = now();
+                pictures(it + 1000);
+                CK(chv_debug_set_switch("CHV_REBIND", "scatter"));
+                double t6 = now();
+                CK(chv_batch_rebind(ctx, kept, items.data(), (int)items.size()));
+                double t7 = now();
+                CK(chv_batch_run(ctx, kept)); CK(chv_pass_end(ctx, 1));
+                double t8 = now();
+                if (it > WARM) { ta.push_back(t1 - t0); tb.push_back(t2 - t1); tc.push_back(t5 - t3); td.push_back(t8 - t6); tc_call.push_back(t4 - t3); td_call.push_back(t7 - t6); }
+            }
+            CK(chv_debug_set_switch("CHV_REBIND", nullptr));
+            CK(chv_batch_destroy(prebuilt)); CK(chv_batch_destroy(kept));
+            std::vector<double> sa = ta;
+            std::sort(sa.begin(), sa.end());
+            printf("%s\"%d\": {\"prebuilt_us\": %.1f, \"prebuilt_min_us\": %.1f, \"prebuilt_p25_us\": %.1f, \"prebuilt_p75_us\": %.1f, \"prebuilt_max_us\": %.1f, \"built_fresh_us\": %.1f, "
+                   "\"rebind_copy_us\": %.1f, \"rebind_scatter_us\": %.1f, \"rebind_copy_call_us\": %.1f, \"rebind_scatter_call_us\": %.1f, \"items\": %d}", first ? "" : ", ", G,
+                   median(ta), sa.front(), sa[sa.size() / 4], sa[sa.size() * 3 / 4], sa.back(), median(tb), median(tc), median(td), median(tc_call), median(td_call), (int)items.size());
+            first = false;
+        }
+        printf("}\n");
+        return 0;
     }
     const int NL = mixer ? 3 : LAYERS;
     for (int G : { 8, 64, mixer ? 128 : 256 }) {
