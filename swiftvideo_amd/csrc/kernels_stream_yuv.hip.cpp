@@ -27,12 +27,14 @@
 //     NEXT trip's first wait (gfx950 counts loads and stores in one counter); chroma leaves once per 16 rows as in tick_yuv_wave.
 // The arithmetic per pixel and layer is tick_yuv_wave's, operation for operation (the reference's unit-scale Khronos arithmetic:
 // c / 255 correctly rounded per tap, unfused sums in source order; code-scale fused taps and the 16.16 matrix for the `_int`
-// kind), so the bytes are those of oracle/ref_kernels.c::px_yuv_to_yuv / px_rgb_to_yuv / px_rgb_to_yuv_int, layer by layer.
+// kind), so the bytes are those of oracle/ref_kernels.c::px_yuv_to_yuv / px_rgb_to_yuv / px_rgb_to_yuv_int, layer by layer.  Every row
+// loop of this file takes it from yuv_rows.hip.h; here are the places of the taps and the forms only this kernel has (fast_rgb_trip, ys_put_raw_k).
 //
 // Eligibility (yuv_stream_eligible): cleared canvas with W % 8 == 0 and H % 4 == 0, 1..4 layers, every layer axis-aligned, bounded,
 // without fill paint and without flips, horizontal reduction <= 1.7 (YUV) / 1.17 (RGB), vertical <= 2.1 (a step of 8 rows must span at most 15 source rows: yuv_stream_eligible), source rows a multiple of
 // 16 bytes, at most 16 KB of rings per wave.  Everything else keeps tick_yuv_wave.
 #include "wave_common.hip.h"
+#include "yuv_rows.hip.h"
 #include "switches.h"
 
 #include <algorithm>
@@ -305,41 +307,6 @@ CHV_DEV int ring_row(const RingState &R, int r) {
 template <class RC>
 CHV_DEV int ring_next(int off) { return off + RC::PITCH == RC::BYTES ? 0 : off + RC::PITCH; }
 
-// ---- pixel arithmetic (tick_yuv_wave's, kernels_wave_yuv.hip.cpp) ----------------------------------------------------------------
-CHV_DEV float ys_t8(uint32_t byte) { return unorm8(byte); }                       // c / 255.0f, correctly rounded
-template <int K>
-CHV_DEV float ys_t8k(uint32_t w) { return unorm8f(K == 0 ? (float)(w & 255u) : K == 1 ? (float)((w >> 8) & 255u) : K == 2 ? (float)((w >> 16) & 255u) : (float)(w >> 24)); }
-template <int K>
-CHV_DEV float ys_ubk(uint32_t w) { return K == 0 ? ub0(w) : K == 1 ? ub1(w) : K == 2 ? ub2(w) : ub3(w); }
-// convert_uchar_sat_rte(f * 255) into byte K of w (v_cvt_pk_u8_f32: RTE, clamp to [0, 255], NaN -> 0 = to_code)
-template <int K>
-CHV_DEV uint32_t ys_put(uint32_t w, float f) {
-    const float v = f * 255.0f;
-    if (K == 0) asm("v_cvt_pk_u8_f32 %0, %1, 0, %0" : "+v"(w) : "v"(v));
-    if (K == 1) asm("v_cvt_pk_u8_f32 %0, %1, 1, %0" : "+v"(w) : "v"(v));
-    if (K == 2) asm("v_cvt_pk_u8_f32 %0, %1, 2, %0" : "+v"(w) : "v"(v));
-    if (K == 3) asm("v_cvt_pk_u8_f32 %0, %1, 3, %0" : "+v"(w) : "v"(v));
-    return w;
-}
-template <int K>
-CHV_DEV uint32_t ys_put_raw(uint32_t w, float v) {
-    if (K == 0) asm("v_cvt_pk_u8_f32 %0, %1, 0, %0" : "+v"(w) : "v"(v));
-    if (K == 1) asm("v_cvt_pk_u8_f32 %0, %1, 1, %0" : "+v"(w) : "v"(v));
-    if (K == 2) asm("v_cvt_pk_u8_f32 %0, %1, 2, %0" : "+v"(w) : "v"(v));
-    if (K == 3) asm("v_cvt_pk_u8_f32 %0, %1, 3, %0" : "+v"(w) : "v"(v));
-    return w;
-}
-CHV_DEV float ys_mix4(float w00, float w10, float w01, float w11, float t00, float t10, float t01, float t11) {
-    return ((w00 * t00 + w10 * t10) + w01 * t01) + w11 * t11;      // lin_mix's order (OpenCL 1.2 section 8.2)
-}
-CHV_DEV int ys_dpp_even(int v) { return __builtin_amdgcn_update_dpp(v, v, 0xA0 /* quad_perm [0,0,2,2] */, 0xf, 0xf, false); }
-CHV_DEV float ys_dpp_even(float v) { return __int_as_float(ys_dpp_even(__float_as_int(v))); }
-
-template <typename F, int... J>
-CHV_DEV void ys_seq_impl(F &f, std::integer_sequence<int, J...>) { (f(std::integral_constant<int, J>{}), ...); }
-template <int N, typename F>
-CHV_DEV void ys_seq(F &f) { ys_seq_impl(f, std::make_integer_sequence<int, N>{}); }
-
 // per-lane column entry of one layer
 struct YsCol {
     uint32_t off;      // byte offsets of the two tap columns inside a ring row, CLAMP_TO_EDGE resolved: plane 0 (luma byte / RGB texel) in bits
@@ -481,10 +448,10 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
         rY[l].last = min(max(__builtin_amdgcn_readfirstlane(ry), -1), S0.h - 1) + 1;
         if (!rgb) {
             // chroma: both lanes of a column pair sample at the EVEN lane's column
-            const int cc_q = ys_dpp_even(cc);
-            const float cca_q = ys_dpp_even(cca);
+            const int cc_q = quad_even(cc);
+            const float cca_q = quad_even(cca);
             const int pw = lane_pic ? 1 : 0;
-            const bool pic_q = ys_dpp_even(pw) != 0;
+            const bool pic_q = quad_even(pw) != 0;
             const unsigned long long validq = __ballot(pic_q);
             picmask |= pic_q ? (1u << (8 + l)) : 0u;
             col[l].ca = cca_q;
@@ -505,7 +472,7 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
         }
         col[l].off = (uint32_t)o0 | ((uint32_t)o1 << 9) | ((uint32_t)c0 << 18) | ((uint32_t)c1 << 25);
     };
-    ys_seq<NL>(setup_layer);
+    for_rows<NL>(setup_layer);
     // (only layer 0 can touch this strip and chunk: an opaque YUV picture whose columns take the short form of the row loops, luma and chroma)
     const bool fast0 = CHV_YS_CARRY && HAS_YUV && (hit & 0xFF) == 1 && (lf[0] & 17) == 16 && (hit & (1 << 16)) != 0 && (hit & (1 << 24)) != 0;
     // (the same for the encoder side's frame: only layer 0, an integer-matrix RGB picture drawn at its own size over the whole strip)
@@ -537,11 +504,7 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
     auto finish_trip = [&](int j0, uint32_t lw, uint32_t cu, uint32_t cv) {
         // ---- the trip's luma: a 4 x 4 byte transpose inside every quad of lanes turns "4 rows of one column" into "4 columns of one row" ----
         {
-            const uint32_t sel1 = (lane & 1) ? 0x03070105u : 0x06020400u, sel2 = (lane & 2) ? 0x03020706u : 0x05040100u;
-            const uint32_t p1 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)lw, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
-            const uint32_t aa = __builtin_amdgcn_perm(p1, lw, sel1);
-            const uint32_t p2 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)aa, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
-            pend_lw = __builtin_amdgcn_perm(p2, aa, sel2);
+            pend_lw = quad_transpose(lw, quad_sel(lane));
             // (lane 4 c + r holds row r, columns 4 c .. 4 c + 3; lane 16 r + c takes it: a quarter wave then holds 64 contiguous bytes of one row)
             if (CHV_YS_STORE & 1) pend_lw = (uint32_t)__builtin_amdgcn_ds_bpermute((4 * (lane & 15) + (lane >> 4)) * 4, (int)pend_lw);
             pend_row = y0 + j0;
@@ -553,21 +516,8 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
             nu = __builtin_amdgcn_perm(cu, nu, sel);
             nv = __builtin_amdgcn_perm(cv, nv, sel);
             if (m == 3 || j0 + 4 >= nrows) {
-                // lane 2k: rows 0, 2, 4, 6 of chroma column k; lane 2k + 1: rows 1, 3, 5, 7  ->  lane 8c + i: row i (+ 4 for lanes 8c + 4 ..) of
-                // columns 4c .. 4c + 3 (kernels_wave_yuv.hip.cpp)
-                const uint32_t selp = (lane & 1) ? 0x03070206u : 0x05010400u;
-                const int srcl = ((lane & ~7) + 2 * (lane & 3) + ((lane >> 2) & 1)) * 4;
-                const uint32_t sel1 = (lane & 1) ? 0x03070105u : 0x06020400u, sel2 = (lane & 2) ? 0x03020706u : 0x05040100u;
-                auto regroup = [&](uint32_t v) {
-                    const uint32_t p = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)v, 0xB1, 0xf, 0xf, false);
-                    uint32_t q = __builtin_amdgcn_perm(p, v, selp);
-                    q = (uint32_t)__builtin_amdgcn_ds_bpermute(srcl, (int)q);
-                    const uint32_t p1 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)q, 0xB1, 0xf, 0xf, false);
-                    const uint32_t bq = __builtin_amdgcn_perm(p1, q, sel1);
-                    const uint32_t p2 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)bq, 0x4E, 0xf, 0xf, false);
-                    return __builtin_amdgcn_perm(p2, bq, sel2);
-                };
-                const uint32_t tu = regroup(nu), tv = regroup(nv);
+                // lane 8c + i: row i (+ 4 for lanes 8c + 4 ..) of chroma columns 4c .. 4c + 3
+                const uint32_t tu = chroma_regroup(nu, lane), tv = chroma_regroup(nv, lane);
                 const int g0 = j0 & ~15;                                             // first row of the group inside the chunk
                 const int crow = (lane & 3) + 4 * ((lane >> 2) & 1);
                 const uint32_t ccol = (uint32_t)((x0 >> 1) + 4 * (lane >> 3));
@@ -630,21 +580,17 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                         constexpr bool FULL = decltype(full_c)::value;
                         int q = ring_row<RingY>(rY[l], ry0);
                         const uint8_t *p = ldsY + (q + o0);
-                        float t0 = ys_t8(p[0]), t1 = FULL ? ys_t8(p[1]) : ys_t8(ldsY[q + o1]);
+                        float t0 = T8(p[0]), t1 = FULL ? T8(p[1]) : T8(ldsY[q + o1]);
                         auto row = [&](auto kc) {
                             constexpr int k = decltype(kc)::value;
                             const float bw = rya[k], ib = 1.0f - bw;
                             q = ring_next<RingY>(q);
                             const uint8_t *p1 = ldsY + (q + o0);
-                            const float b0 = ys_t8(p1[0]), b1 = FULL ? ys_t8(p1[1]) : ys_t8(ldsY[q + o1]);
-                            float v;
-                            if constexpr (FULL) { const float wt = 0.5f * ib, wb = 0.5f * bw; v = ys_mix4(wt, wt, wb, wb, t0, t1, b0, b1); }
-                            else v = ys_mix4(ia * ib, a * ib, ia * bw, a * bw, t0, t1, b0, b1);
-                            t0 = b0; t1 = b1;
-                            const uint32_t nlw = ys_put<k>(lw, v);          // opacity == 1: cur * 0 + luma * 1 = luma exactly
+                            const float v = mix4_carried(t0, t1, T8(p1[0]), FULL ? T8(p1[1]) : T8(ldsY[q + o1]), FULL ? tap_weights_half(bw, ib) : tap_weights(a, ia, bw, ib));
+                            const uint32_t nlw = put_code<k>(lw, v);          // opacity == 1: cur * 0 + luma * 1 = luma exactly
                             if constexpr (FULL) lw = nlw; else lw = lane_pic ? nlw : lw;
                         };
-                        ys_seq<4>(row);
+                        for_rows<4>(row);
                     };
                     auto luma_any = [&](auto opaque_c) {
                         constexpr bool OP = decltype(opaque_c)::value;
@@ -660,12 +606,11 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                             const float bw = rya[k], ib = 1.0f - bw;
                             const int q0 = ring_row<RingY>(rY[l], r), q1 = ring_next<RingY>(q0);
                             const uint8_t *p0 = ldsY + q0, *p1 = ldsY + q1;
-                            const float v = ys_mix4(ia * ib, a * ib, ia * bw, a * bw, ys_t8(p0[o0]), ys_t8(p0[o1]), ys_t8(p1[o0]), ys_t8(p1[o1]));
-                            const float o = OP ? v : ys_t8k<k>(lw) * ialpha + v * alpha;
-                            const uint32_t nlw = ys_put<k>(lw, o);
+                            const float v = mix4(tap_weights(a, ia, bw, ib), T8(p0[o0]), T8(p0[o1]), T8(p1[o0]), T8(p1[o1]));
+                            const uint32_t nlw = yuv_store<k>(lw, v, OP, alpha, ialpha);
                             lw = (lane_pic && act[k]) ? nlw : lw;
                         };
-                        ys_seq<4>(row);
+                        for_rows<4>(row);
                     };
                     if (full) luma_unit(std::true_type{});
                     else if (unit) luma_unit(std::false_type{});
@@ -698,20 +643,18 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                             const int q00 = ring_row<RC>(rC[l], rc0), q01 = ring_next<RC>(q00);
                             const int q20 = FULL ? q01 : ring_row<RC>(rC[l], rc2), q21 = ring_next<RC>(q20);
                             const uint8_t *p0 = ldsC + ((par ? q20 : q00) + c0), *p1 = ldsC + ((par ? q21 : q01) + c0);
-                            float fu, fv;
                             if constexpr (FULL) {
-                                const float wt = 0.5f * icb, wb = 0.5f * cbw;
-                                fu = ys_mix4(wt, wt, wb, wb, ys_t8(p0[0]), ys_t8(p0[BPC]), ys_t8(p1[0]), ys_t8(p1[BPC]));
-                                fv = ys_mix4(wt, wt, wb, wb, ys_t8(p0[VO]), ys_t8(p0[VO + BPC]), ys_t8(p1[VO]), ys_t8(p1[VO + BPC]));
-                                cu = ys_put<0>(cu, fu); cv = ys_put<0>(cv, fv);
+                                const TapWeights cw = tap_weights_half(cbw, icb);
+                                const float fu = mix4(cw, T8(p0[0]), T8(p0[BPC]), T8(p1[0]), T8(p1[BPC]));
+                                const float fv = mix4(cw, T8(p0[VO]), T8(p0[VO + BPC]), T8(p1[VO]), T8(p1[VO + BPC]));
+                                cu = put_code<0>(cu, fu); cv = put_code<0>(cv, fv);
                             } else {
                                 const int dc = ys_c1(col[l].off) - c0;
                                 const float ca = col[l].ca, ica = 1.0f - ca;
-                                const float c00 = ica * icb, c10 = ca * icb, c01 = ica * cbw, c11 = ca * cbw;
-                                fu = ys_mix4(c00, c10, c01, c11, ys_t8(p0[0]), ys_t8(p0[dc]), ys_t8(p1[0]), ys_t8(p1[dc]));
-                                fv = ys_mix4(c00, c10, c01, c11, ys_t8(p0[VO]), ys_t8(p0[VO + dc]), ys_t8(p1[VO]), ys_t8(p1[VO + dc]));
-                                const uint32_t nnu = ys_put<0>(cu, opaque ? fu : ys_t8k<0>(cu) * ialpha + fu * alpha);
-                                const uint32_t nnv = ys_put<0>(cv, opaque ? fv : ys_t8k<0>(cv) * ialpha + fv * alpha);
+                                const TapWeights cw = tap_weights(ca, ica, cbw, icb);
+                                const float fu = mix4(cw, T8(p0[0]), T8(p0[dc]), T8(p1[0]), T8(p1[dc]));
+                                const float fv = mix4(cw, T8(p0[VO]), T8(p0[VO + dc]), T8(p1[VO]), T8(p1[VO + dc]));
+                                const uint32_t nnu = yuv_store<0>(cu, fu, opaque, alpha, ialpha), nnv = yuv_store<0>(cv, fv, opaque, alpha, ialpha);
                                 cu = tkc ? nnu : cu; cv = tkc ? nnv : cv;
                             }
                         };
@@ -753,72 +696,40 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                             if (!(CHV_YS_CARRY && have_row == ryk)) {
                                 const uint8_t *p0 = ldsY + q0;
                                 const uint32_t u00 = fix(*(const uint32_t *)(p0 + o0)), u10 = fix(*(const uint32_t *)(p0 + o1));
-                                if constexpr (INT) {
-                                    t00 = ub0(u00); t01 = ub1(u00); t02 = ub2(u00); t03 = ub3(u00);
-                                    t10 = ub0(u10); t11 = ub1(u10); t12 = ub2(u10); t13 = ub3(u10);
-                                } else {
-                                    t00 = ys_t8k<0>(u00); t01 = ys_t8k<1>(u00); t02 = ys_t8k<2>(u00); t03 = ys_t8k<3>(u00);
-                                    t10 = ys_t8k<0>(u10); t11 = ys_t8k<1>(u10); t12 = ys_t8k<2>(u10); t13 = ys_t8k<3>(u10);
-                                }
+                                const TexelPair n = INT ? texels_code(u00, u10) : texels_unit(u00, u10);
+                                t00 = n.r0; t01 = n.g0; t02 = n.b0; t03 = n.a0; t10 = n.r1; t11 = n.g1; t12 = n.b1; t13 = n.a1;
                             }
-                            const float w00 = ia * ib, w10 = a * ib, w01 = ia * bw, w11 = a * bw;
-                            float b00, b01, b02, b03, b10, b11, b12, b13;
-                            if constexpr (INT) {
-                                b00 = ub0(u01); b01 = ub1(u01); b02 = ub2(u01); b03 = ub3(u01);
-                                b10 = ub0(u11); b11 = ub1(u11); b12 = ub2(u11); b13 = ub3(u11);
-                            } else {
-                                b00 = ys_t8k<0>(u01); b01 = ys_t8k<1>(u01); b02 = ys_t8k<2>(u01); b03 = ys_t8k<3>(u01);
-                                b10 = ys_t8k<0>(u11); b11 = ys_t8k<1>(u11); b12 = ys_t8k<2>(u11); b13 = ys_t8k<3>(u11);
-                            }
+                            const TexelPair t{ t00, t01, t02, t03, t10, t11, t12, t13 };
+                            const TapWeights w = tap_weights(a, ia, bw, ib);
+                            const TexelPair bt = INT ? texels_code(u01, u11) : texels_unit(u01, u11);
                             const float curf = (float)__builtin_amdgcn_ubfe(lw, (uint32_t)(8 * k), 8u);      // the pixel's luma code
                             const bool even_row = (k & 1) == 0;
                             if constexpr (INT) {
-                                const float q0f = cs_mix(w00, w10, w01, w11, t00, t10, b00, b10);
-                                const float q1f = cs_mix(w00, w10, w01, w11, t01, t11, b01, b11);
-                                const float q2f = cs_mix(w00, w10, w01, w11, t02, t12, b02, b12);
-                                const float q3f = cs_mix(w00, w10, w01, w11, t03, t13, b03, b13);
-                                // to_code_raw of a convex combination of codes: no clamp can trigger; rint through the float adder
-                                // (the multiplier's operands keep the adder's bias: r2y_base_biased, pixel_math.hip.h)
-                                const int cr = (int)code_biased(q0f), cg = (int)code_biased(q1f), cb = (int)code_biased(q2f);
-                                const float a2 = q3f * ka, ia2 = 1.f - a2;
-                                const float py = fixed_to_codef(r2y_row(kk.y[0], kk.y[1], kk.y[2], r2y_base_biased(kk.y[0], kk.y[1], kk.y[2], (kk.yoff << 16) + 32768), cr, cg, cb));
-                                const uint32_t nlw = ys_put_raw_k(lw, __builtin_fmaf(py, a2, curf * ia2), k);
+                                const IntPixel px = rgb_int_pixel(w, t, bt, ka);
+                                const uint32_t nlw = ys_put_raw_k(lw, __builtin_fmaf(r2y_luma(kk, px), px.a2, curf * px.ia2), k);
                                 lw = tk ? nlw : lw;
                                 if (even_row) {
-                                    // chroma of the quad: the even lane's pixel of this (even) row; the trip's second chroma row lives in the odd
-                                    // lane (the values travel one lane up, quad_perm [0, 0, 2, 2])
-                                    float pu = fixed_to_codef(r2y_row(kk.u[0], kk.u[1], kk.u[2], r2y_base_biased(kk.u[0], kk.u[1], kk.u[2], (128 << 16) + 32768), cr, cg, cb));
-                                    float pv = fixed_to_codef(r2y_row(kk.v[0], kk.v[1], kk.v[2], r2y_base_biased(kk.v[0], kk.v[1], kk.v[2], (128 << 16) + 32768), cr, cg, cb));
-                                    float sa = a2, sia = ia2;
-                                    int stk = (tk && owner_lane) ? 1 : 0;
-                                    if (k == 2) { pu = ys_dpp_even(pu); pv = ys_dpp_even(pv); sa = ys_dpp_even(a2); sia = ys_dpp_even(ia2); stk = ys_dpp_even(stk); }
-                                    const bool mine = stk != 0 && par == (k >> 1);
-                                    const uint32_t nnu = ys_put_raw<0>(cu, __builtin_fmaf(pu, sa, ub0(cu) * sia));
-                                    const uint32_t nnv = ys_put_raw<0>(cv, __builtin_fmaf(pv, sa, ub0(cv) * sia));
+                                    // (the trip's second chroma row, k == 2, lives in the odd lane: quad_chroma)
+                                    float pu = r2y_cb(kk, px), pv = r2y_cr(kk, px), sa = px.a2, sia = px.ia2;
+                                    const bool mine = quad_chroma(pu, pv, sa, sia, tk && owner_lane, k == 2) && par == (k >> 1);
+                                    const uint32_t nnu = put_code_raw<0>(cu, __builtin_fmaf(pu, sa, ub0(cu) * sia));
+                                    const uint32_t nnv = put_code_raw<0>(cv, __builtin_fmaf(pv, sa, ub0(cv) * sia));
                                     cu = mine ? nnu : cu; cv = mine ? nnv : cv;
                                 }
                             } else {
-                                const float r = ys_mix4(w00, w10, w01, w11, t00, t10, b00, b10);
-                                const float g = ys_mix4(w00, w10, w01, w11, t01, t11, b01, b11);
-                                const float bl = ys_mix4(w00, w10, w01, w11, t02, t12, b02, b12);
-                                const float q3f = ys_mix4(w00, w10, w01, w11, t03, t13, b03, b13);
-                                const float a2 = q3f * opacity, ia2 = 1.f - a2;
-                                float yy, uu, vv;
-                                rgb2yuv(r * a2, g * a2, bl * a2, yy, uu, vv);
+                                const YuvPixel px = rgb_float_pixel(w, t, bt, opacity);
                                 // (no fill: `cur * (1 - 0) + f * 0` is cur, and its clamp to [-1, 1] is the identity on a code / 255)
-                                const uint32_t nlw = ys_put_raw_k(lw, (unorm8f(curf) * ia2 + yy * a2) * 255.0f, k);
+                                const uint32_t nlw = ys_put_raw_k(lw, (unorm8f(curf) * px.ia2 + px.yy * px.a2) * 255.0f, k);
                                 lw = tk ? nlw : lw;
                                 if (even_row) {
-                                    float su = uu, sv = vv, sa = a2, sia = ia2;
-                                    int stk = (tk && owner_lane) ? 1 : 0;
-                                    if (k == 2) { su = ys_dpp_even(uu); sv = ys_dpp_even(vv); sa = ys_dpp_even(a2); sia = ys_dpp_even(ia2); stk = ys_dpp_even(stk); }
-                                    const bool mine = stk != 0 && par == (k >> 1);
-                                    const uint32_t nnu = ys_put<0>(cu, ys_t8k<0>(cu) * sia + su * sa);
-                                    const uint32_t nnv = ys_put<0>(cv, ys_t8k<0>(cv) * sia + sv * sa);
+                                    float su = px.uu, sv = px.vv, sa = px.a2, sia = px.ia2;
+                                    const bool mine = quad_chroma(su, sv, sa, sia, tk && owner_lane, k == 2) && par == (k >> 1);
+                                    const uint32_t nnu = put_code<0>(cu, T8k<0>(cu) * sia + su * sa);
+                                    const uint32_t nnv = put_code<0>(cv, T8k<0>(cv) * sia + sv * sa);
                                     cu = mine ? nnu : cu; cv = mine ? nnv : cv;
                                 }
                             }
-                            t00 = b00; t01 = b01; t02 = b02; t03 = b03; t10 = b10; t11 = b11; t12 = b12; t13 = b13;
+                            t00 = bt.r0; t01 = bt.g0; t02 = bt.b0; t03 = bt.a0; t10 = bt.r1; t11 = bt.g1; t12 = bt.b1; t13 = bt.a1;
                             have_row = ryk + 1;
                         }
                     };
@@ -827,7 +738,7 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                 }
             }
         };
-        ys_seq<NL>(layer);
+        for_rows<NL>(layer);
         finish_trip(j0, lw, cu, cv);
     };
 
@@ -861,15 +772,12 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                   ccv_ = r2y_base_biased(kv0, kv1, kv2, (128 << 16) + 32768);
         const float ka = opac[0] * kInv255;
         // (texels are taken as R, G, B, A whatever the source order: a swizzled source has R in byte 2 and B in byte 0 — which byte a
-        // conversion reads is free, a v_perm_b32 per texel in front of the conversions was not)
-        auto red = [](uint32_t w) { return SWZ ? ub2(w) : ub0(w); };
-        auto blue = [](uint32_t w) { return SWZ ? ub0(w) : ub2(w); };
+        // conversion reads is free, a v_perm_b32 per texel in front of the conversions was not: texels_code<SWZ>)
         int q = ring_row<RingR>(rY[0], ry0);
         if (rt_row != ry0) {
             const uint8_t *p0 = ldsY + (q + o0);
-            const uint32_t u00 = *(const uint32_t *)p0, u10 = *(const uint32_t *)(p0 + 4);
-            rt00 = red(u00); rt01 = ub1(u00); rt02 = blue(u00); rt03 = ub3(u00);
-            rt10 = red(u10); rt11 = ub1(u10); rt12 = blue(u10); rt13 = ub3(u10);
+            const TexelPair n = texels_code<SWZ>(*(const uint32_t *)p0, *(const uint32_t *)(p0 + 4));
+            rt00 = n.r0; rt01 = n.g0; rt02 = n.b0; rt03 = n.a0; rt10 = n.r1; rt11 = n.g1; rt12 = n.b1; rt13 = n.a1;
         }
         uint32_t lw = 0, cu = 128u, cv = 128u;
         auto row = [&](auto kc) {
@@ -877,34 +785,23 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
             const float bw = rya[k], ib = 1.0f - bw;
             q = ring_next<RingR>(q);
             const uint8_t *p1 = ldsY + (q + o0);
-            const uint32_t u01 = *(const uint32_t *)p1, u11 = *(const uint32_t *)(p1 + 4);
-            const float b00 = red(u01), b01 = ub1(u01), b02 = blue(u01), b03 = ub3(u01);
-            const float b10 = red(u11), b11 = ub1(u11), b12 = blue(u11), b13 = ub3(u11);
-            const float wt = 0.5f * ib, wb = 0.5f * bw;
-            const float q0f = cs_mix(wt, wt, wb, wb, rt00, rt10, b00, b10);
-            const float q1f = cs_mix(wt, wt, wb, wb, rt01, rt11, b01, b11);
-            const float q2f = cs_mix(wt, wt, wb, wb, rt02, rt12, b02, b12);
-            const float q3f = cs_mix(wt, wt, wb, wb, rt03, rt13, b03, b13);
-            rt00 = b00; rt01 = b01; rt02 = b02; rt03 = b03; rt10 = b10; rt11 = b11; rt12 = b12; rt13 = b13;
-            // to_code_raw of a convex combination of codes: no clamp can trigger; rint through the float adder
-            const int cr = (int)code_biased(q0f), cg = (int)code_biased(q1f), cb = (int)code_biased(q2f);
-            const float a2 = q3f * ka, ia2 = 1.f - a2;
-            const float py = fixed_to_codef(mad24_uniform(cr, ky0, mad24_uniform(cg, ky1, mad24_uniform(cb, ky2, cy_))));
-            lw = ys_put_raw<k>(lw, py * a2);
+            const TexelPair bt = texels_code<SWZ>(*(const uint32_t *)p1, *(const uint32_t *)(p1 + 4));
+            const IntPixel px = rgb_int_pixel(tap_weights_half(bw, ib), TexelPair{ rt00, rt01, rt02, rt03, rt10, rt11, rt12, rt13 }, bt, ka);
+            rt00 = bt.r0; rt01 = bt.g0; rt02 = bt.b0; rt03 = bt.a0; rt10 = bt.r1; rt11 = bt.g1; rt12 = bt.b1; rt13 = bt.a1;
+            const float py = fixed_to_codef(mad24_uniform(px.cr, ky0, mad24_uniform(px.cg, ky1, mad24_uniform(px.cb, ky2, cy_))));
+            lw = put_code_raw<k>(lw, py * px.a2);
             if constexpr ((k & 1) == 0) {
-                // chroma of the quad: the even lane's pixel of this (even) row; the trip's second chroma row lives in the odd lane (the values
-                // travel one lane up, quad_perm [0, 0, 2, 2])
-                float pu = fixed_to_codef(mad24_uniform(cr, ku0, mad24_uniform(cg, ku1, mad24_uniform(cb, ku2, ccu_))));
-                float pv = fixed_to_codef(mad24_uniform(cr, kv0, mad24_uniform(cg, kv1, mad24_uniform(cb, kv2, ccv_))));
-                float sa = a2, sia = ia2;
-                if constexpr (k == 2) { pu = ys_dpp_even(pu); pv = ys_dpp_even(pv); sa = ys_dpp_even(a2); sia = ys_dpp_even(ia2); }
-                const bool mine = par == (k >> 1);            // (every column of the strip is inside the picture and the canvas)
-                const uint32_t nnu = ys_put_raw<0>(cu, __builtin_fmaf(pu, sa, ub0(cu) * sia));
-                const uint32_t nnv = ys_put_raw<0>(cv, __builtin_fmaf(pv, sa, ub0(cv) * sia));
+                // (the trip's second chroma row lives in the odd lane; every column of the strip is inside the picture and the canvas)
+                float pu = fixed_to_codef(mad24_uniform(px.cr, ku0, mad24_uniform(px.cg, ku1, mad24_uniform(px.cb, ku2, ccu_))));
+                float pv = fixed_to_codef(mad24_uniform(px.cr, kv0, mad24_uniform(px.cg, kv1, mad24_uniform(px.cb, kv2, ccv_))));
+                float sa = px.a2, sia = px.ia2;
+                const bool mine = quad_chroma<true>(pu, pv, sa, sia, true, k == 2) && par == (k >> 1);
+                const uint32_t nnu = put_code_raw<0>(cu, __builtin_fmaf(pu, sa, ub0(cu) * sia));
+                const uint32_t nnv = put_code_raw<0>(cv, __builtin_fmaf(pv, sa, ub0(cv) * sia));
                 cu = mine ? nnu : cu; cv = mine ? nnv : cv;
             }
         };
-        ys_seq<4>(row);
+        for_rows<4>(row);
         rt_row = ry0 + 4;
         finish_trip(j0, lw, cu, cv);
     };
@@ -940,7 +837,7 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
         const int o0 = ys_o0(col[0].off), c0 = ys_c0(col[0].off);
         int q = ring_row<RingY>(rY[0], lo), qc = ring_row<RCc>(rC[0], clo);
         float t0, t1;
-        { const uint8_t *p = ldsY + (q + o0); t0 = ys_t8(p[0]); t1 = ys_t8(p[1]); }
+        { const uint8_t *p = ldsY + (q + o0); t0 = T8(p[0]); t1 = T8(p[1]); }
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const uint4 w4 = *(const uint4 *)(tab + YS_TAB + 4 * h);
@@ -951,23 +848,19 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                 const float bw = rya[k], ib = 1.0f - bw;
                 q = ring_next<RingY>(q);
                 const uint8_t *p1 = ldsY + (q + o0);
-                const float b0 = ys_t8(p1[0]), b1 = ys_t8(p1[1]);
-                const float wt = 0.5f * ib, wb = 0.5f * bw;
-                const float v = ys_mix4(wt, wt, wb, wb, t0, t1, b0, b1);
-                t0 = b0; t1 = b1;
-                lw = ys_put<k>(lw, v);
+                lw = put_code<k>(lw, mix4_carried(t0, t1, T8(p1[0]), T8(p1[1]), tap_weights_half(bw, ib)));
             };
-            ys_seq<4>(row);
+            for_rows<4>(row);
             {
                 // chroma rows 2 m (even lanes: taps qc, qc + 1) and 2 m + 1 (odd lanes: qc + 1, qc + 2)
                 const uint4 cw4 = *(const uint4 *)(tab + 2 * YS_TAB + 4 * h);
                 const float cbw = __uint_as_float(par ? cw4.z : cw4.x), icb = 1.0f - cbw;
                 const int q1 = ring_next<RCc>(qc), q2 = ring_next<RCc>(q1);
                 const uint8_t *p0 = ldsC + ((par ? q1 : qc) + c0), *p1 = ldsC + ((par ? q2 : q1) + c0);
-                const float wt = 0.5f * icb, wb = 0.5f * cbw;
-                const float fu = ys_mix4(wt, wt, wb, wb, ys_t8(p0[0]), ys_t8(p0[BPC]), ys_t8(p1[0]), ys_t8(p1[BPC]));
-                const float fv = ys_mix4(wt, wt, wb, wb, ys_t8(p0[VO]), ys_t8(p0[VO + BPC]), ys_t8(p1[VO]), ys_t8(p1[VO + BPC]));
-                cu = ys_put<0>(cu, fu); cv = ys_put<0>(cv, fv);
+                const TapWeights cw = tap_weights_half(cbw, icb);
+                const float fu = mix4(cw, T8(p0[0]), T8(p0[BPC]), T8(p1[0]), T8(p1[BPC]));
+                const float fv = mix4(cw, T8(p0[VO]), T8(p0[VO + BPC]), T8(p1[VO]), T8(p1[VO + BPC]));
+                cu = put_code<0>(cu, fu); cv = put_code<0>(cv, fv);
                 qc = q2;
             }
             if (h == 1) flush();
@@ -1032,7 +925,7 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                     t[3 * YS_TAB + (lane >> 2) + 1] = (uint32_t)(rc + 1) | ((uint32_t)(rc6 + 1) << 13);
                 }
             };
-            ys_seq<NL>(fill);
+            for_rows<NL>(fill);
             wave_lds_fence();
         }
         // ---- residency, once per 8-row step: the YUV layers' rings take the rows the step's two trips tap -------------------------------
@@ -1070,7 +963,7 @@ CHV_DEV void ys_body(const DTick *__restrict__ ticks, const DLayer *__restrict__
                         else ring_ensure<RingC2>(rC[l], ringY + (uint32_t)RingY::BYTES, srcC, clo, chi, issued, lane);
                     }
                 };
-                ys_seq<NL>(step);
+                for_rows<NL>(step);
             }
         }
         if constexpr (KINDS == YK_RGBINT) {

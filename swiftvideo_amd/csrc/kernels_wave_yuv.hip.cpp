@@ -15,8 +15,12 @@
 //   * strips that lie entirely inside a layer's picture run branch-free; every other strip (picture or border edges, fill
 //     paint, unstaged rectangles) applies the layer pixel by pixel with the general kernel's own code (yuv_pixel.hip.h).
 // Bytes: those of kernels_general.hip.cpp = oracle/ref_kernels.c (px_yuv_to_yuv, px_rgb_to_yuv), layer by layer.
+// The code helpers, the quad_perm lane move, the store shuffles and the integer-matrix row (int_rows) are yuv_rows.hip.h's.  The YUV body and
+// the float RGB row spell out the same operations as that header's functions, in the same order (through them hipcc swaps the operands of
+// some commutative adds and multiplies in this kernel: profiles/yuv_rows_notes.md): a change to those two is made in the header AND here.
 #include "wave_common.hip.h"
 #include "yuv_pixel.hip.h"
+#include "yuv_rows.hip.h"
 #include "switches.h"
 #include "geom_cache.h"
 // 0: this translation unit — the kernels that compute their geometry, eligibility, the launcher, the geometry tables' builder; 1:
@@ -41,49 +45,6 @@
 #pragma clang fp contract(off)
 
 namespace chv {
-
-// UNORM8 loads: c / 255.0f, correctly rounded — the two-term product of pixel_math.hip.h (cvt + mul + fma per byte; a single multiply is wrong
-// for 126 of 256 codes).  A 256-entry LDS table in their place was measured in rounds 2 and 6 and is gone from the source
-// (profiles/r06_unorm_table_experiment.patch, r06_notes.md section 3): it removes 8 % of the launch's vector instructions and is 6 % SLOWER on
-// conflict-free content (gradients: 4.9 M bank-conflict cycles), 6-7 % on low-pass noise (34 M), 6-10 % on random bytes (121 M) — an LDS read
-// occupies the CU's one LDS pipe for as long as one of its four SIMDs would have spent on the arithmetic.
-CHV_DEV float T8(uint32_t byte) { return unorm8(byte); }
-// the same for byte K of a packed word
-template <int K>
-CHV_DEV float T8k(uint32_t w) {
-    return unorm8f(K == 0 ? (float)(w & 255u) : K == 1 ? (float)((w >> 8) & 255u) : K == 2 ? (float)((w >> 16) & 255u) : (float)(w >> 24));
-}
-// convert_uchar_sat_rte(f * 255) into byte K of w (v_cvt_pk_u8_f32: RTE, clamp to [0, 255], NaN -> 0 = to_code)
-template <int K>
-CHV_DEV uint32_t put_code(uint32_t w, float f) {
-    const float v = f * 255.0f;
-    if (K == 0) asm("v_cvt_pk_u8_f32 %0, %1, 0, %0" : "+v"(w) : "v"(v));
-    if (K == 1) asm("v_cvt_pk_u8_f32 %0, %1, 1, %0" : "+v"(w) : "v"(v));
-    if (K == 2) asm("v_cvt_pk_u8_f32 %0, %1, 2, %0" : "+v"(w) : "v"(v));
-    if (K == 3) asm("v_cvt_pk_u8_f32 %0, %1, 3, %0" : "+v"(w) : "v"(v));
-    return w;
-}
-// row(integral_constant<int, j>) for j = 0 .. YTH - 1, in order (the row index is a compile-time constant in the body: byte
-// positions of the packed canvas codes are immediates)
-template <typename F, int... J>
-CHV_DEV void for_each_row_impl(F &f, std::integer_sequence<int, J...>) { (f(std::integral_constant<int, J>{}), ...); }
-template <int N, typename F>
-CHV_DEV void for_rows(F &f) { for_each_row_impl(f, std::make_integer_sequence<int, N>{}); }
-
-// code-scale variants (the integer-matrix RGB kind): byte K of a word as a float; to_code_raw of a code-scale value into byte K
-template <int K>
-CHV_DEV float ubk(uint32_t w) { return K == 0 ? ub0(w) : K == 1 ? ub1(w) : K == 2 ? ub2(w) : ub3(w); }
-template <int K>
-CHV_DEV uint32_t put_code_raw(uint32_t w, float v) {
-    if (K == 0) asm("v_cvt_pk_u8_f32 %0, %1, 0, %0" : "+v"(w) : "v"(v));
-    if (K == 1) asm("v_cvt_pk_u8_f32 %0, %1, 1, %0" : "+v"(w) : "v"(v));
-    if (K == 2) asm("v_cvt_pk_u8_f32 %0, %1, 2, %0" : "+v"(w) : "v"(v));
-    if (K == 3) asm("v_cvt_pk_u8_f32 %0, %1, 3, %0" : "+v"(w) : "v"(v));
-    return w;
-}
-CHV_DEV float mix4(float w00, float w10, float w01, float w11, float t00, float t10, float t01, float t11) {
-    return ((w00 * t00 + w10 * t10) + w01 * t01) + w11 * t11;      // lin_mix's order (OpenCL 1.2 section 8.2)
-}
 
 #ifndef CHV_WAVEY_CARRY
 #define CHV_WAVEY_CARRY 1
@@ -240,12 +201,12 @@ __global__ __launch_bounds__(WAVE_BLOCK, ((KINDS == 1 || KINDS == 2) ? CHV_WAVEY
             // ---- YUV picture over the whole strip (kernels.cl.swift:78-94): cur * (1 - opacity) + sample * opacity ----
             const float alpha = U[U_OPACITY], ialpha = 1.f - alpha;
             const float a = cur.cya, ia = 1.0f - a;
-            // the even lane's column entry in both lanes of a pair (quad_perm [0, 0, 2, 2])
-            const int cco_q = __builtin_amdgcn_update_dpp(cur.cco, cur.cco, 0xA0, 0xf, 0xf, false);
-            const float cca_q = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(cur.cca), __float_as_int(cur.cca), 0xA0, 0xf, 0xf, false));
+            // the even lane's column entry in both lanes of a pair
+            const int cco_q = quad_even(cur.cco);
+            const float cca_q = quad_even(cur.cca);
             const float icaq = 1.0f - cca_q;
             const int picw = lane_pic && col_in ? 1 : 0;
-            const bool pic_q = __builtin_amdgcn_update_dpp(picw, picw, 0xA0, 0xf, 0xf, false) != 0;
+            const bool pic_q = quad_even(picw) != 0;
             auto body = [&](auto planar_c, auto opaque_c) {
                 constexpr bool PL = decltype(planar_c)::value, OP = decltype(opaque_c)::value;
                 // (unit_rows: native-resolution layers — the lower luma tap row of a pixel is the upper one of the pixel below, its
@@ -327,9 +288,8 @@ __global__ __launch_bounds__(WAVE_BLOCK, ((KINDS == 1 || KINDS == 2) ? CHV_WAVEY
             float t00 = 0.f, t01 = 0.f, t02 = 0.f, t03 = 0.f, t10 = 0.f, t11 = 0.f, t12 = 0.f, t13 = 0.f;
             if (carry) {
                 const uint8_t *p0 = smem + (row_fast<YTH, false>(rowtab, 0).yoff + cur.cyo);
-                const uint32_t u00 = ((const uint32_t *)p0)[0], u10 = ((const uint32_t *)p0)[1];
-                t00 = ub0(u00); t01 = ub1(u00); t02 = ub2(u00); t03 = ub3(u00);
-                t10 = ub0(u10); t11 = ub1(u10); t12 = ub2(u10); t13 = ub3(u10);
+                const TexelPair n = texels_code(((const uint32_t *)p0)[0], ((const uint32_t *)p0)[1]);
+                t00 = n.r0; t01 = n.g0; t02 = n.b0; t03 = n.a0; t10 = n.r1; t11 = n.g1; t12 = n.b1; t13 = n.a1;
             }
             auto int_rows = [&](auto fill_c, auto carry_c) {
                 constexpr bool FILL = decltype(fill_c)::value;      // !FILL: clamp(fma(f, 0, c * 1), 0, 255) = c for a code c
@@ -341,46 +301,25 @@ __global__ __launch_bounds__(WAVE_BLOCK, ((KINDS == 1 || KINDS == 2) ? CHV_WAVEY
                     const float b = rw.yb, ib = rw.iyb;
                     const uint8_t *p0 = smem + (rw.yoff + cur.cyo);
                     const uint32_t u01 = ((const uint32_t *)(p0 + p0pitch))[0], u11 = ((const uint32_t *)(p0 + p0pitch))[1];
-                    const float w00 = ia * ib, w10 = a * ib, w01 = ia * b, w11 = a * b;
-                    // staged texels are R, G, B, A whatever the source order
-                    const float b00 = ub0(u01), b01 = ub1(u01), b02 = ub2(u01), b03 = ub3(u01);
-                    const float b10 = ub0(u11), b11 = ub1(u11), b12 = ub2(u11), b13 = ub3(u11);
+                    const TapWeights w = tap_weights(a, ia, b, ib);
+                    const TexelPair bt = texels_code(u01, u11);      // staged texels are R, G, B, A whatever the source order
                     if constexpr (!CARRY) {
-                        const uint32_t u00 = ((const uint32_t *)p0)[0], u10 = ((const uint32_t *)p0)[1];
-                        t00 = ub0(u00); t01 = ub1(u00); t02 = ub2(u00); t03 = ub3(u00);
-                        t10 = ub0(u10); t11 = ub1(u10); t12 = ub2(u10); t13 = ub3(u10);
+                        const TexelPair n = texels_code(((const uint32_t *)p0)[0], ((const uint32_t *)p0)[1]);
+                        t00 = n.r0; t01 = n.g0; t02 = n.b0; t03 = n.a0; t10 = n.r1; t11 = n.g1; t12 = n.b1; t13 = n.a1;
                     }
-                    const float q0 = cs_mix(w00, w10, w01, w11, t00, t10, b00, b10);
-                    const float q1 = cs_mix(w00, w10, w01, w11, t01, t11, b01, b11);
-                    const float q2 = cs_mix(w00, w10, w01, w11, t02, t12, b02, b12);
-                    const float q3 = cs_mix(w00, w10, w01, w11, t03, t13, b03, b13);
-                    if constexpr (CARRY) { t00 = b00; t01 = b01; t02 = b02; t03 = b03; t10 = b10; t11 = b11; t12 = b12; t13 = b13; }
-                    // to_code_raw of a convex combination of codes: no clamp can trigger; rint through the float adder
-                    // (the multiplier's operands keep the adder's bias: r2y_base_biased, pixel_math.hip.h)
-                    const int cr = (int)code_biased(q0), cg = (int)code_biased(q1), cb = (int)code_biased(q2);
-                    const float a2 = q3 * ka, ia2 = 1.f - a2;
-                    const float py = fixed_to_codef(r2y_row(k.y[0], k.y[1], k.y[2], r2y_base_biased(k.y[0], k.y[1], k.y[2], (k.yoff << 16) + 32768), cr, cg, cb));
+                    const IntPixel px = rgb_int_pixel(w, TexelPair{ t00, t01, t02, t03, t10, t11, t12, t13 }, bt, ka);
+                    if constexpr (CARRY) { t00 = bt.r0; t01 = bt.g0; t02 = bt.b0; t03 = bt.a0; t10 = bt.r1; t11 = bt.g1; t12 = bt.b1; t13 = bt.a1; }
+                    const float py = r2y_luma(k, px);
                     uint32_t &lw = ly[j >> 2];
                     const float cyf = ubk<j & 3>(lw);
                     const float r0 = FILL ? clampf(__builtin_fmaf(fyf, af, cyf * iaf), 0.f, 255.f) : cyf;
-                    const uint32_t nlw = put_code_raw<j & 3>(lw, __builtin_fmaf(py, a2, r0 * ia2));
+                    const uint32_t nlw = put_code_raw<j & 3>(lw, __builtin_fmaf(py, px.a2, r0 * px.ia2));
                     lw = tk ? nlw : lw;
                     if constexpr ((j & 1) == 0) {
-                        // chroma of the quad: the even lane's pixel of this (even) row; chroma row jj = j / 2 lives in the even lane
-                        // (jj even) or in its odd neighbour (jj odd: the values travel one lane up, quad_perm [0, 0, 2, 2])
+                        // chroma row jj = j / 2 lives in the even lane (jj even) or in its odd neighbour (jj odd): quad_chroma
                         constexpr int jj = j >> 1, m = jj >> 1;
-                        float pu = fixed_to_codef(r2y_row(k.u[0], k.u[1], k.u[2], r2y_base_biased(k.u[0], k.u[1], k.u[2], (128 << 16) + 32768), cr, cg, cb));
-                        float pv = fixed_to_codef(r2y_row(k.v[0], k.v[1], k.v[2], r2y_base_biased(k.v[0], k.v[1], k.v[2], (128 << 16) + 32768), cr, cg, cb));
-                        float sa = a2, sia = ia2;
-                        int stk = (tk && owner_lane) ? 1 : 0;
-                        if constexpr ((jj & 1) != 0) {
-                            pu = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pu), __float_as_int(pu), 0xA0, 0xf, 0xf, false));
-                            pv = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(pv), __float_as_int(pv), 0xA0, 0xf, 0xf, false));
-                            sa = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(a2), __float_as_int(a2), 0xA0, 0xf, 0xf, false));
-                            sia = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ia2), __float_as_int(ia2), 0xA0, 0xf, 0xf, false));
-                            stk = __builtin_amdgcn_update_dpp(stk, stk, 0xA0, 0xf, 0xf, false);
-                        }
-                        const bool mine = stk != 0 && par == (jj & 1);
+                        float pu = r2y_cb(k, px), pv = r2y_cr(k, px), sa = px.a2, sia = px.ia2;
+                        const bool mine = quad_chroma(pu, pv, sa, sia, tk && owner_lane, (jj & 1) != 0) && par == (jj & 1);
                         const float cuf = ubk<m>(nu), cvf = ubk<m>(nv);
                         const float r1 = FILL ? clampf(__builtin_fmaf(fuf, af, cuf * iaf), 0.f, 255.f) : cuf;
                         const float r2 = FILL ? clampf(__builtin_fmaf(fvf, af, cvf * iaf), 0.f, 255.f) : cvf;
@@ -440,16 +379,16 @@ __global__ __launch_bounds__(WAVE_BLOCK, ((KINDS == 1 || KINDS == 2) ? CHV_WAVEY
                 lw = tk ? nlw : lw;
                 if constexpr ((j & 1) == 0) {
                     // the quad's chroma comes from the even lane's pixel of this (even) row; chroma row jj = j / 2 lives in the even
-                    // lane (jj even) or in its odd neighbour (jj odd: the values travel one lane up, quad_perm [0, 0, 2, 2])
+                    // lane (jj even) or in its odd neighbour (jj odd: the values travel one lane up: quad_even)
                     constexpr int jj = j >> 1, m = jj >> 1;
                     float su = uu, sv = vv, sa = a2, sia = ia2;
                     int stk = (tk && owner_lane) ? 1 : 0;
                     if constexpr ((jj & 1) != 0) {
-                        su = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(uu), __float_as_int(uu), 0xA0, 0xf, 0xf, false));
-                        sv = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(vv), __float_as_int(vv), 0xA0, 0xf, 0xf, false));
-                        sa = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(a2), __float_as_int(a2), 0xA0, 0xf, 0xf, false));
-                        sia = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ia2), __float_as_int(ia2), 0xA0, 0xf, 0xf, false));
-                        stk = __builtin_amdgcn_update_dpp(stk, stk, 0xA0, 0xf, 0xf, false);
+                        su = quad_even(uu);
+                        sv = quad_even(vv);
+                        sa = quad_even(a2);
+                        sia = quad_even(ia2);
+                        stk = quad_even(stk);
                     }
                     const bool mine = stk != 0 && par == (jj & 1);
                     const float ry = clampf(T8k<m>(nu) * iaf + fua, -1.f, 1.f);
@@ -487,9 +426,9 @@ __global__ __launch_bounds__(WAVE_BLOCK, ((KINDS == 1 || KINDS == 2) ? CHV_WAVEY
                 for (int k = 0; k < YLW; k++) ly[k] = (j >> 2) == k ? lw : ly[k];
                 // back to the lane that holds the row (all lanes of the wave execute this: the loop runs over uniform j)
                 const int ow = owner ? 1 : 0;
-                const uint32_t bu = (uint32_t)__builtin_amdgcn_update_dpp((int)pu, (int)pu, 0xA0, 0xf, 0xf, false);
-                const uint32_t bv = (uint32_t)__builtin_amdgcn_update_dpp((int)pv, (int)pv, 0xA0, 0xf, 0xf, false);
-                const bool bo = __builtin_amdgcn_update_dpp(ow, ow, 0xA0, 0xf, 0xf, false) != 0;
+                const uint32_t bu = (uint32_t)quad_even((int)pu);
+                const uint32_t bv = (uint32_t)quad_even((int)pv);
+                const bool bo = quad_even(ow) != 0;
                 const bool mine = (j & 1) == 0 && bo && par == (from_odd ? 1 : 0);
                 if (mine) { nu = (nu & ~(255u << csh)) | (bu << csh); nv = (nv & ~(255u << csh)) | (bv << csh); }
             }
@@ -513,34 +452,25 @@ __global__ __launch_bounds__(WAVE_BLOCK, ((KINDS == 1 || KINDS == 2) ? CHV_WAVEY
                           ((((uintptr_t)PY.ptr | (uintptr_t)PC.ptr | (uintptr_t)PV.ptr) & 3u) == 0) && (((PY.pitch | PC.pitch | PV.pitch) & 3) == 0);
         const int lane = S.lane;
         if (wide) {
-            const uint32_t sel1 = (lane & 1) ? 0x03070105u : 0x06020400u, sel2 = (lane & 2) ? 0x03020706u : 0x05040100u;
-            auto quad_transpose = [&](uint32_t v) {
-                const uint32_t p1 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)v, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
-                const uint32_t a = __builtin_amdgcn_perm(p1, v, sel1);
-                const uint32_t p2 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)a, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
-                return __builtin_amdgcn_perm(p2, a, sel2);
-            };
+            const QuadSel qs = quad_sel(lane);
             const uint32_t loff = (uint32_t)(lane & 3) * (uint32_t)PY.pitch + (uint32_t)(x0 + (lane & ~3));
 #pragma unroll
-            for (int k = 0; k < YLW; k++) gst_at<uint32_t>(PY.ptr + (size_t)(y0 + 4 * k) * PY.pitch, loff, quad_transpose(ly[k]));
+            for (int k = 0; k < YLW; k++) gst_at<uint32_t>(PY.ptr + (size_t)(y0 + 4 * k) * PY.pitch, loff, quad_transpose(ly[k], qs));
         } else if (col_in) {
 #pragma unroll
             for (int j = 0; j < YTH; j++)
                 if (y0 + j < TH) gst_at<uint8_t>(PY.ptr + (size_t)(y0 + j) * PY.pitch, (uint32_t)x, (uint8_t)((ly[j >> 2] >> (8 * (j & 3))) & 255u));
         }
         if (wide && YTH == 16) {
-            // lane 2k: rows 0, 2, 4, 6 of chroma column k; lane 2k + 1: rows 1, 3, 5, 7  ->  lane 2k: rows 0-3, lane 2k + 1: rows 4-7
+            // yuv_rows.hip.h::chroma_regroup, spelled out: through the function hipcc folds `src` differently in the NV12 instantiations
+            // (profiles/yuv_rows_notes.md)
             const uint32_t selp = (lane & 1) ? 0x03070206u : 0x05010400u;
-            const int src = ((lane & ~7) + 2 * (lane & 3) + ((lane >> 2) & 1)) * 4;         // ds_bpermute: lane 8c + i <- column 4c + i (rows 0-3), lane 8c + 4 + i <- the same column (rows 4-7)
-            const uint32_t sel1 = (lane & 1) ? 0x03070105u : 0x06020400u, sel2 = (lane & 2) ? 0x03020706u : 0x05040100u;
+            const int src = ((lane & ~7) + 2 * (lane & 3) + ((lane >> 2) & 1)) * 4;
+            const QuadSel qs = quad_sel(lane);
             auto regroup = [&](uint32_t v) {
                 const uint32_t p = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)v, 0xB1, 0xf, 0xf, false);
-                uint32_t a = __builtin_amdgcn_perm(p, v, selp);
-                a = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)a);
-                const uint32_t p1 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)a, 0xB1, 0xf, 0xf, false);
-                const uint32_t b = __builtin_amdgcn_perm(p1, a, sel1);
-                const uint32_t p2 = (uint32_t)__builtin_amdgcn_update_dpp(dpp_old(), (int)b, 0x4E, 0xf, 0xf, false);
-                return __builtin_amdgcn_perm(p2, b, sel2);                                   // lane 8c + i: row i (+ 4 for lanes 8c + 4 ..), columns 4c .. 4c + 3
+                const uint32_t a = __builtin_amdgcn_perm(p, v, selp);
+                return quad_transpose((uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)a), qs);
             };
             const uint32_t tu = regroup(nu), tv = regroup(nv);
             const uint32_t crow = (uint32_t)((lane & 3) + 4 * ((lane >> 2) & 1)), ccol = (uint32_t)((x0 >> 1) + 4 * (lane >> 3));
