@@ -408,12 +408,25 @@ int chv_run_custom(chv_context *ctx, const char *name, const chv_image *target,
                    const void *uniforms, size_t uniforms_size, int blends);
 
 /* ---- resampling --------------------------------------------------------- */
-/* Separable Lanczos-3 resize of a 4-component image (BGRA or RGBA) from `src`
- * to `dst` size.  No reference counterpart; DESIGN.md section 4.4.  Reductions whose 8 x 4 output tile needs more than 160 KB of staged
- * source (about 24:1 on one axis, about 17:1 on both at once) are refused with CHV_ERR_INVALID_VALUE: nothing is written. */
+/* Separable Lanczos-3 resize of `src` to the size of `dst`, no format conversion.  No reference counterpart; DESIGN.md section 4.4.
+ * Three families, selected by `dst`:
+ *   - one 4-component plane (BGRA or RGBA);
+ *   - CHV_FMT_NV12: 2 planes of 1 and 2 components;
+ *   - CHV_FMT_Y420P: 3 planes of 1 component.
+ * The two 4:2:0 families are PLANE-WISE: every plane of `src` is resampled to the size of the corresponding plane of `dst` as an image of its
+ * own, with the (in, out) tables of its own width and height, every component through the same chain (horizontal then vertical pass, one
+ * fused multiply-add per tap, convert_uchar_sat_rte) — no colour conversion, no chroma re-siting, no cross-plane term; all planes in one launch.
+ * Errors (nothing is launched, nothing is written): a `dst` of any other format or plane structure, or a target plane that fails a plane
+ * check -> CHV_ERR_BAD_TARGET; a `src` whose format and plane structure are not `dst`'s (NV12 -> BGRA, BGRA -> NV12, NV12 -> y420p ...), or a
+ * source plane that fails a plane check -> CHV_ERR_BAD_INPUT; a build without the planar kernels -> CHV_ERR_NOT_IMPLEMENTED for the 4:2:0
+ * families.  Reductions whose 8 x 4 output tile needs more than 160 KB of staged 4-byte source (about 24:1 on one axis, about 17:1 on both at
+ * once) are refused with CHV_ERR_INVALID_VALUE — the rule applies to every plane's own sizes, one refused plane refuses the picture. */
 int chv_scale_lanczos(chv_context *ctx, const chv_image *dst, const chv_image *src);
-/* n resizes of one geometry (every src of one size, every dst of one size) in one launch per CHV_LANCZOS_BATCH_CHUNK pairs;
- * same bytes as n calls of chv_scale_lanczos.  Other geometries in the list -> CHV_ERR_INVALID_VALUE, nothing is launched. */
+/* n resizes of ONE geometry and ONE format (every src of one size, every dst of one size, all of dsts[0]'s family) in one launch per chunk;
+ * same bytes as n calls of chv_scale_lanczos.  Other geometries in the list, a 4:2:0 picture in a list of 4-component planes, a 4-component
+ * plane or the other 4:2:0 format in a list of 4:2:0 pictures -> CHV_ERR_INVALID_VALUE, nothing is launched.
+ * A chunk is what fits one descriptor slot: CHV_LANCZOS_BATCH_CHUNK (dst, src) pairs of 4-component planes, 62 NV12 pictures (2 plane pairs
+ * each) or 41 y420p pictures (3 plane pairs each). */
 #define CHV_LANCZOS_BATCH_CHUNK 64
 int chv_scale_lanczos_batch(chv_context *ctx, const chv_image *dsts, const chv_image *srcs, int n);
 

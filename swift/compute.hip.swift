@@ -498,27 +498,30 @@ func compositeTick(_ context: ComputeContext,
     return context
 }
 
-// MARK: - Lanczos-3 resample, BGRA -> BGRA (no reference counterpart; used by filter.pict.hip.swift)
+// MARK: - Lanczos-3 resample without conversion (no reference counterpart; used by filter.pict.hip.swift)
+// BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p: a 4:2:0 picture is resampled plane by plane, every plane with the tables of its own
+// size, all planes in one launch (chv_scale_lanczos).  Any other pair is an error of the library (badInputData / badTarget).
 
 func scaleLanczos(_ context: ComputeContext, src: PictureSample, target: PictureSample) throws -> ComputeContext {
-    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 1) else {
+    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 3) else {
         throw ComputeError.badTarget
     }
-    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 1) else {
+    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 3) else {
         throw ComputeError.badInputData(description: "Bad input image")
     }
     try check(chv_scale_lanczos(context.handle, &targetDesc, &desc))
     return context
 }
 
-/// n resizes of one geometry in one launch per 64 pairs (chv_scale_lanczos_batch): several PictureFilters / streams per tick
+/// n resizes of one geometry and one format in one launch per chunk (64 BGRA pairs, 62 nv12 or 41 y420p pictures; chv_scale_lanczos_batch):
+/// several PictureFilters / streams per tick
 func scaleLanczos(_ context: ComputeContext, pairs: [(src: PictureSample, target: PictureSample)]) throws -> ComputeContext {
     var targets = [chv_image](), sources = [chv_image]()
     for pair in pairs {
-        guard let targetImage = pair.target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 1) else {
+        guard let targetImage = pair.target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
             throw ComputeError.badTarget
         }
-        guard let image = pair.src.imageBuffer(), let desc = describe(image, maxPlanes: 1) else {
+        guard let image = pair.src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
             throw ComputeError.badInputData(description: "Bad input image")
         }
         targets.append(targetDesc)

@@ -7,7 +7,8 @@
    (Sources/SwiftVideo/filter.pict.swift:20-47): a Tx<PictureSample, PictureSample> with a compute
    context of its own.  This file gives it a body: convert a picture to `outputFormat` at `outputSize`
    on the device — one full-canvas layer through the composite kernels (colour conversion + bilinear
-   scale in one launch) or, for BGRA -> BGRA, a separable Lanczos-3 resample (chv_scale_lanczos).
+   scale in one launch) or, without conversion (BGRA -> BGRA, nv12 -> nv12, y420p -> y420p), a separable
+   Lanczos-3 resample (chv_scale_lanczos; a 4:2:0 picture plane by plane).
    It replaces filter.pict.swift when GPGPU_HIP is defined.
 */
 #if GPGPU_HIP
@@ -56,6 +57,10 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                 strongSelf.context = try usingContext(ctx) {
                     switch strongSelf.scaler {
                     case .lanczos:
+                        let format = strongSelf.outputFormat
+                        guard src.pixelFormat() == format, format == .BGRA || format == .nv12 || format == .y420p else {
+                            throw ComputeError.notImplemented
+                        }
                         return try scaleLanczos($0, src: src, target: dst)
                     case .bilinear:
                         // the unit quad stretched over the whole canvas (what PictureAnimator produces for a

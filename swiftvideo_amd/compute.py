@@ -690,6 +690,8 @@ class TickBatch:
 
 
 def scaleLanczos(ctx, dst, src):
+    """Lanczos-3 resize of `src` to the size of `dst` (chv_scale_lanczos): both one 4-component plane, both nv12 or both y420p — a 4:2:0
+    picture is resampled plane by plane, every plane with the tables of its own size, in one launch."""
     d, s = _image_desc(dst), _image_desc(src)
     if d is None:
         raise ComputeError(4, "target has no GPU image buffer")
@@ -700,7 +702,8 @@ def scaleLanczos(ctx, dst, src):
 
 
 class LanczosBatch:
-    """n Lanczos-3 resizes of one geometry issued as one launch per 64 pairs (CHV_LANCZOS_BATCH_CHUNK; chv_scale_lanczos_batch): what a host with
+    """n Lanczos-3 resizes of one geometry and one format issued as one launch per 64 BGRA pairs (CHV_LANCZOS_BATCH_CHUNK; 62 nv12 or 41
+    y420p pictures; chv_scale_lanczos_batch): what a host with
     several streams per device uses per tick instead of n launches.  pairs: [(dst PictureSample, src PictureSample)]; the
     descriptors are built once, `run` can be called every tick (canvas rings make the same pairs recur)."""
 
@@ -763,7 +766,8 @@ class PictureFilter:
     device — the operator the reference sketches and leaves commented out (filter.pict.swift:20-47: same
     constructor shape: a context of its own, sharing the given one).  One full-canvas layer through the
     composite kernels: colour conversion + bilinear scale in one launch (`scaler="bilinear"`, any format
-    pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`, BGRA -> BGRA).
+    pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: no conversion, BGRA -> BGRA, nv12 -> nv12 or
+    y420p -> y420p, a 4:2:0 picture plane by plane).
     CPU samples are uploaded first; the sample's time stamps, ids and transform state are carried over.
     Results land in a ring of `numberBackingImages` device images like the mixer's (mix.video.swift:148-167)."""
 
@@ -815,8 +819,8 @@ class PictureFilter:
             dst = self._backing(sample)
             beginComputePass(ctx)
             if self.scaler == "lanczos":
-                if src.pixelFormat() != PixelFormat.BGRA or self.outputFormat != PixelFormat.BGRA:
-                    raise ComputeError(9, "lanczos: BGRA -> BGRA only")
+                if src.pixelFormat() != self.outputFormat or self.outputFormat not in (PixelFormat.BGRA, PixelFormat.nv12, PixelFormat.y420p):
+                    raise ComputeError(9, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only")
                 scaleLanczos(ctx, dst, src)
             else:
                 # a full-canvas opaque layer: identity placement, no border, no fill

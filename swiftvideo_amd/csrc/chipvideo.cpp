@@ -26,6 +26,7 @@
 #include "switches.h"
 #include "geom_cache.h"
 #include "rebind.h"
+#include "lanczos_planar.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -110,6 +111,9 @@ Switches &chv::switches() {
 // the scatter kernel's launcher (rebind.h): null until kernels_rebind.hip.cpp registers it, and for good in a build without that unit
 static std::atomic<RebindLauncher> g_rebind_launcher{nullptr};
 void chv::register_rebind_launcher(RebindLauncher fn) { g_rebind_launcher.store(fn, std::memory_order_release); }
+// the planar Lanczos launcher (lanczos_planar.h): null until kernels_lanczos_planar.hip.cpp registers it, and for good in a build without that unit
+static std::atomic<LanczosPlanarLauncher> g_lanczos_planar_launcher{nullptr};
+void chv::register_lanczos_planar_launcher(LanczosPlanarLauncher fn) { g_lanczos_planar_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -2175,9 +2179,128 @@ static int lanczos_table(chv_context *c, int in_size, int out_size, LanczosRef *
     return CHV_OK;
 }
 
+// ---- the 4:2:0 families of chv_scale_lanczos: NV12 (planes of 1 and 2 components) and y420p (three planes of 1), plane by plane ----
+// Pictures per descriptor slot of a batch chunk: a picture's plane pairs must fit one slot together.
+static constexpr int kLanczosChunkNV12 = 62, kLanczosChunkY420P = 41;
+static_assert((size_t)kLanczosChunkNV12 * 2 * 2 * sizeof(DPlane) <= kDescSlotBytes && (size_t)kLanczosChunkY420P * 3 * 2 * sizeof(DPlane) <= kDescSlotBytes,
+              "a chunk's plane pairs must fit one descriptor slot");
+static_assert(kLanczosChunkNV12 <= CHV_LANCZOS_BATCH_CHUNK && kLanczosChunkY420P <= CHV_LANCZOS_BATCH_CHUNK, "no planar chunk is longer than a BGRA one");
+
+// planes of a 4:2:0 Lanczos family, 0 for every other (format, structure)
+static int lanczos_planar_planes(const chv_image *img) {
+    if (!img) return 0;
+    if (img->format == CHV_FMT_NV12 && img->n_planes == 2) return 2;
+    if (img->format == CHV_FMT_Y420P && img->n_planes == 3) return 3;
+    return 0;
+}
+static int lanczos_planar_comps(int format, int plane) { return format == CHV_FMT_NV12 && plane == 1 ? 2 : 1; }
+
+// (dst, src) of one picture -> np plane pairs at out[2 p], out[2 p + 1]; every check of plane_to_device on every plane
+static int lanczos_planar_pairs(chv_context *c, const chv_image *dst, const chv_image *src, int np, int idx, DPlane *out) {
+    if (lanczos_planar_planes(src) != np || src->format != dst->format)
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos source %d must have the target's format and planes (%s, %d planes)", idx, dst->format == CHV_FMT_NV12 ? "nv12" : "y420p", np);
+    for (int p = 0; p < np; p++) {
+        const int comps = lanczos_planar_comps(dst->format, p);
+        int rc = plane_to_device(dst->planes[p], comps, c->device, &out[2 * p], CHV_ERR_BAD_TARGET, "target", p);
+        if (rc) return rc;
+        rc = plane_to_device(src->planes[p], comps, c->device, &out[2 * p + 1], CHV_ERR_BAD_INPUT, "input", p);
+        if (rc) return rc;
+    }
+    return CHV_OK;
+}
+
+// the tables of every plane of one geometry (up to four distinct ones; the references are held until the launch is enqueued)
+static int lanczos_planar_job(chv_context *c, const DPlane *pairs, int np, LanczosRef *refs, LanczosPlanarJob *job) {
+    memset(job, 0, sizeof *job);
+    job->n_planes = np;
+    for (int p = 0; p < np; p++) {
+        const DPlane &d = pairs[2 * p], &s = pairs[2 * p + 1];
+        int rc = lanczos_table(c, s.w, d.w, &refs[2 * p]);
+        if (rc) return rc;
+        rc = lanczos_table(c, s.h, d.h, &refs[2 * p + 1]);
+        if (rc) return rc;
+        const LanczosTable &tx = *refs[2 * p], &ty = *refs[2 * p + 1];
+        job->tab[p] = LanczosPlaneTables{ tx.first, tx.weights, ty.first, ty.weights, tx.taps, ty.taps };
+        job->dst[p] = d; job->src[p] = s;
+    }
+    return CHV_OK;
+}
+
+static int scale_lanczos_planar(chv_context *c, const chv_image *dst, const chv_image *src, int np) {
+    const LanczosPlanarLauncher launcher = g_lanczos_planar_launcher.load(std::memory_order_acquire);
+    DPlane pairs[2 * kLanczosPlanarMaxPlanes];
+    DepScope deps;
+    int rc = lanczos_planar_pairs(c, dst, src, np, 0, pairs);
+    if (rc) return rc;
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    LanczosRef refs[2 * kLanczosPlanarMaxPlanes];
+    LanczosPlanarJob job;
+    rc = lanczos_planar_job(c, pairs, np, refs, &job);
+    if (rc) return rc;
+    job.batch = nullptr; job.n_pictures = 1;
+    (void)hipGetLastError();
+    hipError_t e = launcher(job, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "lanczos launch");
+    return CHV_OK;
+}
+
+static int scale_lanczos_planar_batch(chv_context *c, const chv_image *dsts, const chv_image *srcs, int n, int np) {
+    const LanczosPlanarLauncher launcher = g_lanczos_planar_launcher.load(std::memory_order_acquire);
+    std::vector<DPlane> pairs((size_t)2 * np * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        if (dsts[i].format != dsts[0].format || lanczos_planar_planes(&dsts[i]) != np)
+            return fail(CHV_ERR_INVALID_VALUE, "target %d: format %d with %d planes, the batch is format %d with %d planes (one format per batch)", i,
+                        dsts[i].format, dsts[i].n_planes, dsts[0].format, np);
+        if (srcs[i].format != dsts[0].format || lanczos_planar_planes(&srcs[i]) != np)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d: format %d with %d planes, the batch is format %d with %d planes (one format per batch)", i,
+                        srcs[i].format, srcs[i].n_planes, dsts[0].format, np);
+        DPlane *pi = pairs.data() + (size_t)2 * np * i;
+        int rc = lanczos_planar_pairs(c, &dsts[i], &srcs[i], np, i, pi);
+        if (rc) return rc;
+        for (int q = 0; q < 2 * np; q++)
+            if (pi[q].w != pairs[q].w || pi[q].h != pairs[q].h)
+                return fail(CHV_ERR_INVALID_VALUE, "pair %d, plane %d: %dx%d -> %dx%d, the batch is %dx%d -> %dx%d (one geometry per batch)", i, q / 2,
+                            pi[q | 1].w, pi[q | 1].h, pi[q & ~1].w, pi[q & ~1].h, pairs[q | 1].w, pairs[q | 1].h, pairs[q & ~1].w, pairs[q & ~1].h);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    LanczosRef refs[2 * kLanczosPlanarMaxPlanes];
+    LanczosPlanarJob job;
+    rc = lanczos_planar_job(c, pairs.data(), np, refs, &job);
+    if (rc) return rc;
+    // the plane pairs travel through the descriptor ring, a slot per chunk, like the 4-component batch's
+    const int per_slot = np == 2 ? kLanczosChunkNV12 : kLanczosChunkY420P;
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, pairs.data() + (size_t)2 * np * first, sizeof(DPlane) * 2 * np * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        hipError_t e = launcher(job, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "lanczos launch");
+    }
+    return CHV_OK;
+}
+
 extern "C" int chv_scale_lanczos(chv_context *c, const chv_image *dst, const chv_image *src) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
+    if (const int np = lanczos_planar_planes(dst)) return scale_lanczos_planar(c, dst, src, np);
+    if (dst && (dst->format == CHV_FMT_NV12 || dst->format == CHV_FMT_Y420P))
+        return fail(CHV_ERR_BAD_TARGET, "Lanczos target: a %s image has %d planes, not %d", dst->format == CHV_FMT_NV12 ? "nv12" : "y420p",
+                    dst->format == CHV_FMT_NV12 ? 2 : 3, dst->n_planes);
     if (!dst || dst->n_planes != 1) return fail(CHV_ERR_BAD_TARGET, "Lanczos target must be one 4-component plane");
     if (!src || src->n_planes != 1) return fail(CHV_ERR_BAD_INPUT, "Lanczos source must be one 4-component plane");
     DPlane d, s;
@@ -2207,8 +2330,13 @@ extern "C" int chv_scale_lanczos_batch(chv_context *c, const chv_image *dsts, co
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
     if (n <= 0 || !dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "empty batch");
+    if (const int np = lanczos_planar_planes(&dsts[0])) return scale_lanczos_planar_batch(c, dsts, srcs, n, np);
     std::vector<DPlane> pairs((size_t)2 * n);
     DepScope deps;
+    // (one format per batch: a 4:2:0 picture among 4-component planes is the list's mistake, not the image's — before anything else is looked at)
+    for (int i = 1; i < n; i++)
+        if (lanczos_planar_planes(&dsts[i]) || lanczos_planar_planes(&srcs[i]))
+            return fail(CHV_ERR_INVALID_VALUE, "pair %d is a 4:2:0 picture, the batch began with a 4-component plane (one format per batch)", i);
     for (int i = 0; i < n; i++) {
         if (dsts[i].n_planes != 1) return fail(CHV_ERR_BAD_TARGET, "Lanczos target %d must be one 4-component plane", i);
         if (srcs[i].n_planes != 1) return fail(CHV_ERR_BAD_INPUT, "Lanczos source %d must be one 4-component plane", i);

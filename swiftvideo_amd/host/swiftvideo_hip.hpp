@@ -483,7 +483,8 @@ inline ComputeContext compositeTick(ComputeContext ctx, const PictureSample &tar
     return ctx;
 }
 
-// separable Lanczos-3 resample BGRA -> BGRA (chv_scale_lanczos; no reference counterpart)
+// separable Lanczos-3 resample without conversion (chv_scale_lanczos; no reference counterpart): BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p —
+// a 4:2:0 picture plane by plane, every plane with the tables of its own size, all planes in one launch
 inline ComputeContext scaleLanczos(ComputeContext ctx, const PictureSample &dst, const PictureSample &src) {
     chv_image d, s;
     if (!describe(dst, &d)) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
@@ -492,7 +493,8 @@ inline ComputeContext scaleLanczos(ComputeContext ctx, const PictureSample &dst,
     return ctx;
 }
 
-// n resizes of one geometry as one launch (chv_scale_lanczos_batch): same bytes as n scaleLanczos calls
+// n resizes of one geometry and one format as one launch per chunk (chv_scale_lanczos_batch; 64 BGRA pairs, 62 nv12 or 41 y420p pictures):
+// same bytes as n scaleLanczos calls
 inline ComputeContext scaleLanczos(ComputeContext ctx, const std::vector<std::pair<PictureSample, PictureSample>> &dstSrcPairs) {
     std::vector<chv_image> d(dstSrcPairs.size()), s(dstSrcPairs.size());
     for (size_t i = 0; i < dstSrcPairs.size(); i++) {
@@ -776,7 +778,7 @@ private:
 // ---- PictureFilter: the Tx<PictureSample, PictureSample> the reference sketches and leaves commented out
 //      (filter.pict.swift:20-47).  Converts a picture to outputFormat at outputSize on the device: one
 //      full-canvas layer through the composite kernels (colour conversion + bilinear scale in one launch),
-//      or a separable Lanczos-3 resample (BGRA -> BGRA).  CPU samples are uploaded first; results land in a
+//      or a separable Lanczos-3 resample (no conversion: BGRA -> BGRA, nv12 -> nv12, y420p -> y420p).  CPU samples are uploaded first; results land in a
 //      ring of device images like the mixer's (mix.video.swift:148-167). ------------------------------------
 class PictureFilter {
 public:
@@ -803,8 +805,8 @@ public:
             PictureSample src = sample.bufferType() == BufferType::cpu ? uploadComputePicture(context_, sample) : sample;
             PictureSample dst = getBacking(sample);
             if (scaler_ == Scaler::lanczos) {
-                if (src.pixelFormat() != PixelFormat::BGRA || format_ != PixelFormat::BGRA)
-                    throw ComputeError(CHV_ERR_NOT_IMPLEMENTED, "lanczos: BGRA -> BGRA only");
+                if (src.pixelFormat() != format_ || (format_ != PixelFormat::BGRA && format_ != PixelFormat::nv12 && format_ != PixelFormat::y420p))
+                    throw ComputeError(CHV_ERR_NOT_IMPLEMENTED, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only");
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczos(c, dst, src); });
             } else {
                 // a full-canvas opaque layer: the unit quad stretched over the canvas in NDC, no border, no fill

@@ -8,7 +8,8 @@ Method (conservative, per kernel): the prefetch quads are the destinations of th
 an ordinary compiler-managed load).  Walking the code in program order, a quad is "in flight" from a load into it until the next
 `s_waitcnt vmcnt(n)` with n smaller than the number of prefetch quads; while in flight, any other instruction naming one of its registers is a
 violation.  The code is walked in program order; the kernels' loops are entered with every prefetch quad in flight (the prologue's loads) and come
-back to their top in the same state, so one walk covers the back edge as well.  Prints the violations and exits 1 if there are any."""
+back to their top in the same state, so one walk covers the back edge as well.  `s_waitcnt vmcnt(0)` frees every quad (a kernel with several
+such loops, one behind the other, ends each of them that way).  Prints the violations and exits 1 if there are any."""
 import re
 import sys
 from pathlib import Path
@@ -69,7 +70,12 @@ def check(text, pattern):
                     continue
                 w = re.search(r"s_waitcnt vmcnt\((\d+)\)", l)
                 if w:
-                    if int(w.group(1)) < len(quads):
+                    if int(w.group(1)) == 0:
+                        inflight.clear()                 # nothing is outstanding any more: every quad has arrived
+                        pending_release = False
+                    elif int(w.group(1)) < len(quads):
+                        # (a kernel may hold several copies of its row loop — planar_lanczos_strip<T>: 1 | 2 components x hand-awaited | not;
+                        # the copies that are not hand-awaited hold compiler-managed x4 loads only, whose waits the compiler writes itself)
                         # in order among loads: everything but the youngest `n` has arrived; the walk does not track ages, and the
                         # kernels only ever touch the oldest quad after such a wait, so: the quads touched before the next load are free
                         inflight_after_wait = set(inflight)
