@@ -64,13 +64,14 @@ const char *chv_build_flags(void);
 /* Measurement / test hook: path-selection switches.  Names and values are those of the environment variables read once at
  * first use (CHV_FORCE_GENERAL=1, CHV_BGRA_PATH=wave|tiled|stream, CHV_WAVE_ROWS=8|16, CHV_TILE_ROWS=16|32, CHV_SAME_GEOM=0,
  * CHV_DESC=host|device, CHV_STREAM=0, CHV_YUV_STREAM=0|force, CHV_WAVE_DMA=0, CHV_PASS_FUSE=0, CHV_GEOM_CACHE=0|eager, CHV_STREAM_ROWS=n,
- * CHV_STREAM_OPAQUE=0, CHV_REBIND=scatter|copy);
+ * CHV_STREAM_OPAQUE=0, CHV_STREAM_CARRY=0, CHV_REBIND=scatter|copy);
  * NULL or "" restores the default.  Process-wide, atomic; not part of the Swift-facing contract. */
 int chv_debug_set_switch(const char *name, const char *value);
 /* Measurement / test hook: counters of the current device's store of strip-kernel geometry tables (csrc/geom_cache.h): "geom_store_patched"
  * (launches whose layers were pointed at stored tables before their descriptors travelled: batches at creation, lone ticks),
  * "geom_store_batch_hits", "geom_store_builds", "geom_store_bytes", "geom_store_tables"; and "stream_opaque_launches", the launches of
- * tick_bgra_stream that took the opaque-bottom kernels (process-wide).  Unknown name -> CHV_ERR_INVALID_VALUE. */
+ * tick_bgra_stream that took the opaque-bottom kernels, and "stream_carry_launches", those of them that took the chroma-carry kernels
+ * (process-wide).  Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
 /* ---- kernels: `enum ComputeKernel`, compute.swift:49-74 ------------------ */

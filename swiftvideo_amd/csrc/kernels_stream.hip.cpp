@@ -117,7 +117,8 @@ hipError_t launch_bgra_stream(const DTick *ticks_host, const DLayer *layers_host
     dim3 grid((unsigned)(((total + 7) / 8) * 8));
     const bool planar = layers_host[ticks_host[0].first_layer].kind == LK_BGRA_FROM_Y420P;
     const size_t layer_bytes = planar ? (size_t)st_layer_bytes<1, true>() : (size_t)st_layer_bytes<1, false>();
-    const size_t lds = (size_t)ST_WAVES * ((size_t)nl * layer_bytes + ST_TAB * (sizeof(uint4) + sizeof(uint32_t)));
+    size_t lds = (size_t)ST_WAVES * ((size_t)nl * layer_bytes + ST_TAB * (sizeof(uint4) + sizeof(uint32_t)));
+    if (CHV_STREAM_LDS_MIN > 0) lds = std::max<size_t>(lds, CHV_STREAM_LDS_MIN);      // (occupancy A/Bs: tools/build_variant.sh ... -DCHV_STREAM_LDS_MIN=n)
     // the absorbed form of the colour matrix (pixel_math.hip.h) when every layer's matrix has one — all but BT.601 full range
     bool absorb = CHV_STREAM_ABSORB != 0;
     for (int i = 0; i < n_ticks && absorb; i++)

@@ -1,6 +1,6 @@
 // kernels_stream_body.hip.inc — stream_body, the device code of the tick_bgra_stream kernels, and what it is built with: included by
-// kernels_stream.hip.cpp (the 32 kernels of every eligible launch) and kernels_stream_opq.hip.cpp (the opaque-bottom kernels), each of which
-// instantiates its own __global__ wrappers.  The kernel's description is at the top of kernels_stream.hip.cpp.
+// kernels_stream.hip.cpp (the 32 kernels of every eligible launch), kernels_stream_opq.hip.cpp (the opaque-bottom kernels) and
+// kernels_stream_carry.hip.cpp (the chroma-carry kernels), each of which instantiates its own __global__ wrappers.  The kernel's description is at the top of kernels_stream.hip.cpp.
 #pragma once
 #include "wave_common.hip.h"
 #include "switches.h"
@@ -42,6 +42,10 @@ namespace chv {
 #endif
 #ifndef CHV_STREAM_WAVES
 #define CHV_STREAM_WAVES 6
+#endif
+#ifndef CHV_STREAM_LDS_MIN
+#define CHV_STREAM_LDS_MIN 0      // timing builds (same pixels): a block asks for at least this much LDS — 32768 holds a CU to five blocks of four
+                                  // waves, five waves per SIMD, with the device code untouched (profiles/stream_chroma_carry_notes.md section 1)
 #endif
 
 constexpr float kRintBias = 8388608.0f;       // 2^23 (stream_body: the rounding between two layers)
@@ -105,6 +109,58 @@ CHV_DEV void st_taps_wait(StTaps &t) {
                  : "n"(YOUNGER));
 }
 
+// The chroma-carry form (CRY, kernels_stream_carry.hip.cpp): 4:2:0 chroma is half height, so at the headline's 1.5 : 1 reduction the chroma
+// tap row stays where it was on one canvas row in four and advances by exactly one on the others — the old lower tap row is the new upper
+// one.  The lane KEEPS the chroma bytes of the two ring rows it taps, in two sets indexed by the ring row's parity, and reads only the set
+// whose row is new to it: 4 bytes per layer on three rows in four, none on the fourth, where the transient form reads 8 on every row.
+// A set: [layer][u at tap column 0, u at column 1, v at column 0, v at column 1] of one chroma ring row (NV12: a (u, v) pair per texel).
+template <int NL> struct StCarry { uint32_t c[NL][4]; };
+static_assert(ST_CL == 256, "the offsets of st_carry_read");
+#define CHV_ST_CARRY_LAYER(L, OU, OV) "ds_read_u8 %[c" #L "0], %[a0] offset:" #OU "\n\tds_read_u8 %[c" #L "1], %[a1] offset:" #OU "\n\t" \
+                                      "ds_read_u8 %[c" #L "2], %[a0] offset:" #OV "\n\tds_read_u8 %[c" #L "3], %[a1] offset:" #OV "\n\t"
+#define CHV_ST_CARRY_REGS(S, L, C) [c##L##0] C((S).c[L][0]), [c##L##1] C((S).c[L][1]), [c##L##2] C((S).c[L][2]), [c##L##3] C((S).c[L][3])
+// one ring row's bytes of every layer as ONE group, issued by hand like st_taps_read (a0 / a1: layer 0's U byte at the lane's two tap columns)
+template <int NL>
+CHV_DEV void st_carry_read(StCarry<NL> &s, uint32_t a0, uint32_t a1) {
+    static_assert(NL >= 2 && NL <= 4, "the carry form: two to four layers");
+    if constexpr (NL == 2)
+        asm volatile(CHV_ST_CARRY_LAYER(0, 0, 1) CHV_ST_CARRY_LAYER(1, 256, 257)
+                     : CHV_ST_CARRY_REGS(s, 0, "+v"), CHV_ST_CARRY_REGS(s, 1, "+v") : [a0] "v"(a0), [a1] "v"(a1));
+    else if constexpr (NL == 3)
+        asm volatile(CHV_ST_CARRY_LAYER(0, 0, 1) CHV_ST_CARRY_LAYER(1, 256, 257) CHV_ST_CARRY_LAYER(2, 512, 513)
+                     : CHV_ST_CARRY_REGS(s, 0, "+v"), CHV_ST_CARRY_REGS(s, 1, "+v"), CHV_ST_CARRY_REGS(s, 2, "+v") : [a0] "v"(a0), [a1] "v"(a1));
+    else
+        asm volatile(CHV_ST_CARRY_LAYER(0, 0, 1) CHV_ST_CARRY_LAYER(1, 256, 257) CHV_ST_CARRY_LAYER(2, 512, 513) CHV_ST_CARRY_LAYER(3, 768, 769)
+                     : CHV_ST_CARRY_REGS(s, 0, "+v"), CHV_ST_CARRY_REGS(s, 1, "+v"), CHV_ST_CARRY_REGS(s, 2, "+v"), CHV_ST_CARRY_REGS(s, 3, "+v")
+                     : [a0] "v"(a0), [a1] "v"(a1));
+}
+// a set's registers named as read and written (no instructions): what st_carry_wait ties behind its wait
+template <int NL>
+CHV_DEV void st_carry_tie(StCarry<NL> &s) {
+    if constexpr (NL == 2) asm volatile("" : CHV_ST_CARRY_REGS(s, 0, "+v"), CHV_ST_CARRY_REGS(s, 1, "+v"));
+    else if constexpr (NL == 3) asm volatile("" : CHV_ST_CARRY_REGS(s, 0, "+v"), CHV_ST_CARRY_REGS(s, 1, "+v"), CHV_ST_CARRY_REGS(s, 2, "+v"));
+    else asm volatile("" : CHV_ST_CARRY_REGS(s, 0, "+v"), CHV_ST_CARRY_REGS(s, 1, "+v"), CHV_ST_CARRY_REGS(s, 2, "+v"), CHV_ST_CARRY_REGS(s, 3, "+v"));
+}
+// a layer's four luma taps: transient, read on every row (luma advances by one or two rows per canvas row at 1.5 : 1)
+struct StLuma { uint32_t y00, y10, y01, y11; };
+template <int LO>
+CHV_DEV void st_luma_read(StLuma &t, uint32_t aY00, uint32_t aY10, uint32_t aY01, uint32_t aY11) {
+    asm volatile("ds_read_u8 %0, %4 offset:%8\n\tds_read_u8 %1, %5 offset:%8\n\tds_read_u8 %2, %6 offset:%8\n\tds_read_u8 %3, %7 offset:%8"
+                 : "=&v"(t.y00), "=&v"(t.y10), "=&v"(t.y01), "=&v"(t.y11) : "v"(aY00), "v"(aY10), "v"(aY01), "v"(aY11), "n"(LO));
+}
+template <int YOUNGER>
+CHV_DEV void st_luma_wait(StLuma &t) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(t.y00), "+v"(t.y10), "+v"(t.y01), "+v"(t.y11) : "n"(YOUNGER));
+}
+// Layer 0's wait: the row's chroma groups (if any) were issued in FRONT of layer 0's luma taps and LDS reads complete in order, so this
+// wait covers them as well — both sets are tied behind it, whether this row read them or not.
+template <int NL, int YOUNGER>
+CHV_DEV void st_carry_wait(StLuma &t, StCarry<NL> &even, StCarry<NL> &odd) {
+    st_luma_wait<YOUNGER>(t);
+    st_carry_tie<NL>(even);
+    st_carry_tie<NL>(odd);
+}
+
 // ONE: a launch of one tick whose descriptors are kernel ARGUMENTS (tick_bgra_stream_one below) — `ticks` / `layers` point into the kernarg
 // segment, every field is a scalar load at a constant offset from one base, issued together: no tick -> first_layer -> layer chain of
 // dependent loads in front of a lone tick's waves, and no descriptor copy in front of the launch.
@@ -112,7 +168,8 @@ CHV_DEV void st_taps_wait(StTaps &t) {
 // OPQ: the bottom layer's opacity is exactly 1 in every tick (kernels_stream_opq.hip.cpp; launch_bgra_stream decides; NL >= 2, ABS only): on the
 // cleared canvas its blend RN(code x 1) is the code it already holds as a clamped 16.16 sum, so the layer computes no blend, and layer 1
 // takes that sum times its 1 - opacity through one v_fma_mix_f32 per channel (see `ial24`).
-template <int NL, bool ONE, bool PL, bool ABS, bool OPQ = false>
+// CRY: the chroma taps are carried down the lane from row to row (StCarry above; kernels_stream_carry.hip.cpp: OPQ batch kernels of NV12 sources)
+template <int NL, bool ONE, bool PL, bool ABS, bool OPQ = false, bool CRY = false>
 CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int n_ticks, int strips_x, int chunks_y, int rows_per_chunk) {
     // ST_WAVES independent waves per block, on neighbouring strips (no barrier anywhere): their source windows overlap by a vector or two,
     // and waves of one block start together on one CU — the shared lines are fetched once (HBM traffic 1.47x -> see profiles/r03_notes.md)
@@ -127,6 +184,7 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
     uint32_t *rowpos = (uint32_t *)(rowtab + ST_TAB);             // [ST_TAB] what the scalar unit uses: luma tap row (16 bits) | chroma tap row (15 bits) << 16 | row inside the picture << 31
     const uint32_t lds0 = (uint32_t)(size_t)lds;                  // LDS byte address of the rings (the DMA's M0)
     static_assert(!OPQ || (NL >= 2 && ABS && CHV_STREAM_PMIX), "the opaque-bottom form: two layers or more, absorbed matrices, binary16 blend inputs");
+    static_assert(!CRY || (OPQ && !PL && !ONE && !(CHV_ST_ABL & 4)), "the chroma-carry form: opaque-bottom batch kernels of NV12 sources");
     const int lane = threadIdx.x & 63;
     // XCD-aware numbering: block b runs on XCD b % 8; an XCD owns a contiguous range of (tick, chunk, group of ST_WAVES strips)
     const int groups_x = (strips_x + ST_WAVES - 1) / ST_WAVES;
@@ -224,6 +282,10 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
     asm volatile("" : "+v"(alpha_word));
     int issued = 0, seqY = 0, seqC = 0;                           // load instructions issued so far; the count right after the newest luma / chroma batch
     int nextY = 0, nextC = 0, landY = 0, landC = 0, baseY = 0, baseC = 0;      // ring state: rows below next* are requested, below land* have arrived
+    // CRY: the carried chroma bytes — ring rows (row - baseC) & 1 == 0 in `cset[0]`, the others in `cset[1]` — and the source row each holds
+    // (wave-uniform; no row yet: the chunk's first row reads both)
+    [[maybe_unused]] StCarry<CRY ? NL : 2> cset[2] = {};
+    [[maybe_unused]] int held0 = 0x40000000, held1 = 0x40000000;
     for (int j = 0; j < nrows; j++) {
         // ---- row entries, ST_TAB at a time: lane = row (WaveStrip::setup) ------------------------------------------------
         if ((j & (ST_TAB - 1)) == 0) {
@@ -330,6 +392,78 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
         const float c00 = ica * icb, c10 = ca * icb, c01 = ica * cbw, c11 = ca * cbw;
         float r0 = 0.f, r1 = 0.f, r2 = 0.f;                          // img_clear_bgra: (0, 0, 0, 1) — the canvas pixel as float codes
         [[maybe_unused]] int32_t q0 = 0, q1 = 0, q2 = 0;             // OPQ: the bottom layer's pixel, clamped 16.16 sums
+        if constexpr (CRY) {
+            // ---- the carried chroma: read what is new to the lane, where the transient form reads its taps (behind the ring's await) ----
+            // Tap rows rc (weights c00, c10) and rc + 1 (c01, c11): rc lies in the set of its parity, rc + 1 in the other.  Advance 0 reads
+            // nothing, advance 1 one set, the chunk's first row and any larger advance both.  The registers hold bytes, not ring slots: a
+            // ring request may overwrite a row the lane still carries (the `s_waitcnt lgkmcnt(0)` in front of a request has seen the reads).
+            // (the weights in FRONT of the reads: hipcc's own wait for the row entry they are made of is a full `lgkmcnt(0)`, and behind the
+            // reads it would sit out their round trip before the first multiply — 0.5 % of the launch)
+            asm volatile("" :: "v"(w00), "v"(w10), "v"(w01), "v"(w11), "v"(c00), "v"(c10), "v"(c01), "v"(c11));
+            const int par = (rc - baseC) & 1;
+            const int row0 = rc + par, row1 = rc + 1 - par;
+            if (held0 != row0) {
+                const uint32_t bc = lds0 + (uint32_t)coff(row0 - baseC);
+                st_carry_read<NL>(cset[0], bc + (uint32_t)oc0v, bc + (uint32_t)oc1v);
+                held0 = row0;
+            }
+            if (held1 != row1) {
+                const uint32_t bc = lds0 + (uint32_t)coff(row1 - baseC);
+                st_carry_read<NL>(cset[1], bc + (uint32_t)oc0v, bc + (uint32_t)oc1v);
+                held1 = row1;
+            }
+            // luma as in the transient form: one wait per layer, the next layer's four taps in flight under this layer's arithmetic
+            // (layer 0's wait stands in FRONT of the branch below and covers the row's chroma groups: inside the two copies the carried
+            // registers are only read — redefined there, each would need a copy where the two paths join, and a copy of a register whose
+            // read is still in flight copies the old byte)
+            StLuma lum[2];
+            st_luma_read<0>(lum[0], aY00, aY10, aY01, aY11);
+            st_carry_wait<NL, 0>(lum[0], cset[0], cset[1]);
+            // The reference accumulates top-left, top-right, bottom-left, bottom-right: which set is the top row is the parity, and a select
+            // per byte would cost what the reads saved — the rest of the row exists twice, chosen by one uniform branch (pack and select
+            // included: only `pending` joins).
+            auto rest = [&](auto top_even) {
+                constexpr int TOP = decltype(top_even)::value ? 0 : 1;
+                auto clayer = [&](auto lt) {
+                    constexpr int l = decltype(lt)::value;
+                    if constexpr (l < NL) {
+                        // (every register a copy reads by hand is read AND awaited inside the copy: the next layer's luma taps)
+                        if constexpr (l + 1 < NL) st_luma_read<(l + 1) * ST_YL>(lum[(l + 1) & 1], aY00, aY10, aY01, aY11);
+                        if constexpr (l >= 1 && l + 1 < NL) st_luma_wait<4>(lum[l & 1]);
+                        else if constexpr (l >= 1) st_luma_wait<0>(lum[l & 1]);
+                        const StLuma &t = lum[l & 1];
+                        const uint32_t *ct = cset[TOP].c[l], *cb_ = cset[1 - TOP].c[l];
+                        const float fy = cs_mix_h(w00, w10, w01, w11, tap_h(t.y00), tap_h(t.y10), tap_h(t.y01), tap_h(t.y11));
+                        const float fu = cs_mix_h(c00, c10, c01, c11, tap_h(ct[0]), tap_h(ct[1]), tap_h(cb_[0]), tap_h(cb_[1]));
+                        const float fv = cs_mix_h(c00, c10, c01, c11, tap_h(ct[2]), tap_h(ct[3]), tap_h(cb_[2]), tap_h(cb_[3]));
+                        int32_t cb, cg, cr;
+                        yuv_to_bgr_fixed_absorbed(csc[l], fy, fu, fv, cb, cg, cr);
+                        const float a24 = al24[l];
+                        if constexpr (l == 0) {
+                            q0 = cb; q1 = cg; q2 = cr;
+                            return;
+                        } else if constexpr (l == 1) {
+                            r0 = __builtin_fmaf(a24, (float)code_h(cb), __builtin_fmaf(ial24, (float)code_h(q0), 0.0f));
+                            r1 = __builtin_fmaf(a24, (float)code_h(cg), __builtin_fmaf(ial24, (float)code_h(q1), 0.0f));
+                            r2 = __builtin_fmaf(a24, (float)code_h(cr), __builtin_fmaf(ial24, (float)code_h(q2), 0.0f));
+                        } else {
+                            r0 = __builtin_fmaf(a24, (float)code_h(cb), __builtin_fmaf(r0, ial[l], nrb[l]));
+                            r1 = __builtin_fmaf(a24, (float)code_h(cg), __builtin_fmaf(r1, ial[l], nrb[l]));
+                            r2 = __builtin_fmaf(a24, (float)code_h(cr), __builtin_fmaf(r2, ial[l], nrb[l]));
+                        }
+                        if (l + 1 < NL) { r0 += kRintBias; r1 += kRintBias; r2 += kRintBias; }
+                    }
+                };
+                clayer(std::integral_constant<int, 0>{}); clayer(std::integral_constant<int, 1>{}); clayer(std::integral_constant<int, 2>{}); clayer(std::integral_constant<int, 3>{});
+                uint32_t out;
+                asm("v_cvt_pk_u8_f32 %0, %1, 0, %2" : "=v"(out) : "v"(r0), "v"(alpha_word));
+                asm("v_cvt_pk_u8_f32 %0, %1, 1, %0" : "+v"(out) : "v"(r1));
+                asm("v_cvt_pk_u8_f32 %0, %1, 2, %0" : "+v"(out) : "v"(r2));
+                pending = (lane_pic && row_pic) ? out : alpha_word;
+            };
+            if (par) rest(std::false_type{}); else rest(std::true_type{});
+            continue;
+        }
         // One wait per layer, and the next layer's taps in flight under this layer's arithmetic (a group belongs to the CURRENT row: nothing is
         // read across rows, so the `s_waitcnt lgkmcnt(0)` in front of a ring request still means "the rows being overwritten have been read")
         // (planar sources keep three more plane pointers per layer set and the V offsets: the twelve registers of a second group do not fit

@@ -2,10 +2,16 @@
 // layer is opaque — a mixer's base feed under its overlays, the bench headline's tick.  On the cleared canvas such a layer's blend is its
 // own code: the row computes none for it, and layer 1 takes the code times its 1 - opacity in one v_fma_mix_f32 per channel (stream_body: OPQ;
 // six vector instructions fewer per row).  Same bytes as the kernels it replaces: launch_bgra_stream picks these for 2 - 4 layers of
-// absorbed colour matrices when stream_select.h says so, CHV_STREAM_OPAQUE=0 keeps the others.
+// absorbed colour matrices when stream_select.h says so, CHV_STREAM_OPAQUE=0 keeps the others.  NV12 batches whose chroma advances by at
+// most a row per canvas row go on to tick_bgra_stream_cc (kernels_stream_carry.hip.cpp) from here.
 #include "kernels_stream_body.hip.inc"
+#include "stream_select.h"
 
 namespace chv {
+
+// kernels_stream_carry.hip.cpp: the chroma-carry kernels (NV12 batches of 2 - 4 layers), same grid, LDS and arguments
+hipError_t launch_bgra_stream_carry(int nl, const DTick *ticks, const DLayer *layers, int n_ticks, dim3 grid, size_t lds, int strips_x, int chunks_y, int rows,
+                                    hipStream_t stream);
 
 template <int NL, bool PL, bool ABS>
 __global__ __launch_bounds__(64 * ST_WAVES, CHV_STREAM_WAVES) void tick_bgra_stream_ob(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int n_ticks,
@@ -23,6 +29,12 @@ hipError_t launch_bgra_stream_opaque(const DTick *ticks_host, const DLayer *laye
                                      size_t lds, int strips_x, int chunks_y, int rows, hipStream_t stream) {
     const int nl = ticks_host[0].n_layers;
     if (nl < 2 || nl > 4) return hipErrorInvalidValue;
+    // NV12 batches whose chroma advances by at most one row per canvas row: the chroma taps carried from row to row (stream_select.h)
+    if (stream_chroma_carry(ticks_host, layers_host, n_ticks, planar, !ticks, switches().stream_carry.load(std::memory_order_relaxed))) {
+        const hipError_t err = launch_bgra_stream_carry(nl, ticks, layers, n_ticks, grid, lds, strips_x, chunks_y, rows, stream);
+        if (err == hipSuccess) debug_counters().stream_carry_launches.fetch_add(1, std::memory_order_relaxed);
+        return err;
+    }
     auto go = [&](auto tag, auto pl) {
         constexpr int NL = decltype(tag)::value;
         constexpr bool PL = decltype(pl)::value;

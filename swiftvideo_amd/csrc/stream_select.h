@@ -18,4 +18,23 @@ inline bool stream_opaque_bottom(const DTick *ticks_host, const DLayer *layers_h
     return true;
 }
 
+// The chroma-carry kernels (kernels_stream_carry.hip.cpp) keep a lane's chroma taps from one canvas row to the next and read only the ring
+// rows that are new to it: right for every geometry the opaque-bottom kernels take, but a gain only where the chroma plane advances by AT MOST
+// ONE row per canvas row (two new rows per canvas row are the eight reads of the transient form, paid at five waves per SIMD instead of
+// six).  Chroma rows per canvas row, as bgra_stream_eligible bounds the luma ratio: v = (y / H * 2 - 1) * T5 * X5 + ..., so dv/dy * h = 2 T5 X5 h / H
+// with the chroma plane's h.  Layers 1.. of a tick share layer 0's geometry (LF_SAME_GEOM).  Only launches the opaque-bottom branch takes are
+// asked; they exist for NV12 batches — planar sources and the by-value lone tick keep tick_bgra_stream_ob.  `enabled`: CHV_STREAM_CARRY.
+inline bool stream_chroma_carry(const DTick *ticks_host, const DLayer *layers_host, int n_ticks, bool planar, bool by_value, int enabled) {
+    if (!enabled || planar || by_value || n_ticks < 1) return false;
+    for (int i = 0; i < n_ticks; i++) {
+        const DTick &T = ticks_host[i];
+        if (T.n_layers < 2 || T.n_layers > 4 || T.H < 1) return false;
+        const DLayer &Y = layers_host[T.first_layer];
+        const double ky = 2.0 * (double)Y.u[U_TRANSFORM + 5] * (double)Y.u[U_TEXTURE + 5];
+        const double sc = ky * Y.src.pl[1].h / (double)T.H;
+        if (!(sc > 0.0) || !(sc <= 1.0)) return false;
+    }
+    return true;
+}
+
 }  // namespace chv

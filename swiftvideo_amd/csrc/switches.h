@@ -2,7 +2,7 @@
 //
 // The environment is read ONCE, at the first use in the process (getenv on a hot path is undefined behaviour next to a
 // setenv in another thread, and the mixer and uploader threads run concurrently): CHV_FORCE_GENERAL, CHV_BGRA_PATH,
-// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE, CHV_REBIND.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
+// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE, CHV_STREAM_CARRY, CHV_REBIND.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
 // never through the environment.  Every value is an atomic int; 0 = "the library decides".
 #pragma once
 #include <atomic>
@@ -32,6 +32,9 @@ struct Switches {
                                          // and the kernel's row table is refilled every 32); 0 (default) launch_bgra_stream decides
     std::atomic<int> stream_opaque{1};   // CHV_STREAM_OPAQUE: 0 launches whose bottom layers are all opaque keep tick_bgra_stream's general kernels (A/B and
                                          // parity tests); 1 (default) they take the opaque-bottom kernels (kernels_stream_opq.hip.cpp)
+    std::atomic<int> stream_carry{1};    // CHV_STREAM_CARRY: 0 opaque-bottom launches keep the kernels that read every chroma tap on every row (A/B and parity
+                                         // tests); 1 (default) NV12 batches whose chroma advances by at most one row per canvas row take the chroma-carry
+                                         // kernels (kernels_stream_carry.hip.cpp; stream_select.h)
     std::atomic<int> rebind{0};          // CHV_REBIND, how chv_batch_rebind sends the new plane addresses: scatter (1) the scatter kernel (kernels_rebind.hip.cpp)
                                          // wherever the batch has a pooled block and the unit is linked; copy (2) the whole descriptor block again (A/B, and
                                          // the only way without them); 0 (default) the library decides (profiles/batch_rebind_notes.md)
@@ -42,6 +45,7 @@ Switches &switches();                    // (chipvideo.cpp; initialised from the
 // link without the kernel units (tests/stubhip), so the kernel units count here instead of exporting a reader.
 struct DebugCounters {
     std::atomic<unsigned long long> stream_opaque_launches{0};       // launches of tick_bgra_stream that took the opaque-bottom kernels
+    std::atomic<unsigned long long> stream_carry_launches{0};        // ... of which: the chroma-carry kernels (kernels_stream_carry.hip.cpp)
 };
 DebugCounters &debug_counters();
 
