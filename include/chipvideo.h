@@ -430,6 +430,23 @@ int chv_scale_lanczos(chv_context *ctx, const chv_image *dst, const chv_image *s
  * each) or 41 y420p pictures (3 plane pairs each). */
 #define CHV_LANCZOS_BATCH_CHUNK 64
 int chv_scale_lanczos_batch(chv_context *ctx, const chv_image *dsts, const chv_image *srcs, int n);
+/* Lanczos-3 resize of one BGRA or RGBA plane INTO an NV12 or y420p picture of `dst`'s size, in one launch: the encoder side's rendition.
+ * the codes chv_scale_lanczos would write for `src` -> plane 0 of `dst`, red, green and blue taken by `src->format`;
+ * luma of every pixel and Cb, Cr of the rounded mean of the 2 x 2 codes a chroma texel covers through the integer matrix of section 4.5 for
+ * `opts->colorspace & 3` (opts == NULL: BT.601 limited).  Alpha is not used; nothing is blended with what `dst` held.  Stream order, upload
+ * dependencies and a pass's held work are those of chv_scale_lanczos.
+ * Errors (nothing is launched, nothing is written):
+ *   - `dst` is not CHV_FMT_NV12 with 2 planes (1 and 2 components) or CHV_FMT_Y420P with 3 planes (1 component), a target plane fails a plane
+ *     check, or a chroma plane is not max(1, w / 2) x max(1, h / 2) of plane 0's w x h                        -> CHV_ERR_BAD_TARGET;
+ *   - `src` is not one 4-component plane whose format is CHV_FMT_BGRA or CHV_FMT_RGBA, or that plane fails a plane check -> CHV_ERR_BAD_INPUT;
+ *   - a reduction chv_scale_lanczos refuses for `src` -> plane 0 of `dst` (the 160 KB rule above)            -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit                                                                        -> CHV_ERR_NOT_IMPLEMENTED. */
+int chv_scale_lanczos_to_yuv(chv_context *ctx, const chv_image *dst, const chv_image *src, const chv_kernel_opts *opts);
+/* n such conversions of ONE geometry, ONE source format, ONE target format and the one colourspace of `opts` in one launch per chunk; same bytes
+ * as n calls of chv_scale_lanczos_to_yuv.  Another geometry, source format or target format in the list -> CHV_ERR_INVALID_VALUE, nothing is
+ * launched; every other error as above; n == 0 is a no-op.  A chunk is what fits one descriptor slot: 83 pictures into NV12 (3 planes each) or
+ * 62 into y420p (4 planes each). */
+int chv_scale_lanczos_to_yuv_batch(chv_context *ctx, const chv_image *dsts, const chv_image *srcs, int n, const chv_kernel_opts *opts);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

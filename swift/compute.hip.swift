@@ -530,4 +530,44 @@ func scaleLanczos(_ context: ComputeContext, pairs: [(src: PictureSample, target
     try check(chv_scale_lanczos_batch(context.handle, &targets, &sources, Int32(pairs.count)))
     return context
 }
+
+// MARK: - Lanczos-3 resize of a BGRA / RGBA picture into an nv12 or y420p picture (no reference counterpart; used by filter.pict.hip.swift)
+// One launch (chv_scale_lanczos_to_yuv, DESIGN.md section 4.4.2): the codes scaleLanczos would write, luma per pixel and chroma of their 2 x 2
+// box mean through the integer BT.601/709 matrix of `colorspace` (chv_colorspace; BT.601 limited by default) — the encoder side's rendition
+// (composer.swift:52-56, enc.video.ffmpeg.swift:211-224).
+
+func scaleLanczosToYuv(_ context: ComputeContext, src: PictureSample, target: PictureSample,
+                       colorspace: Int32 = 0) throws -> ComputeContext {
+    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 3) else {
+        throw ComputeError.badTarget
+    }
+    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 3) else {
+        throw ComputeError.badInputData(description: "Bad input image")
+    }
+    var opts = chv_kernel_opts()
+    opts.colorspace = colorspace
+    try check(chv_scale_lanczos_to_yuv(context.handle, &targetDesc, &desc, &opts))
+    return context
+}
+
+/// n such conversions of one geometry, one source format, one target format and one colourspace in one launch per chunk (83 pictures into
+/// nv12, 62 into y420p; chv_scale_lanczos_to_yuv_batch): the renditions of several streams per tick
+func scaleLanczosToYuv(_ context: ComputeContext, pairs: [(src: PictureSample, target: PictureSample)],
+                       colorspace: Int32 = 0) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for pair in pairs {
+        guard let targetImage = pair.target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+            throw ComputeError.badTarget
+        }
+        guard let image = pair.src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        targets.append(targetDesc)
+        sources.append(desc)
+    }
+    var opts = chv_kernel_opts()
+    opts.colorspace = colorspace
+    try check(chv_scale_lanczos_to_yuv_batch(context.handle, &targets, &sources, Int32(pairs.count), &opts))
+    return context
+}
 #endif

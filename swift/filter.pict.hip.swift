@@ -7,8 +7,9 @@
    (Sources/SwiftVideo/filter.pict.swift:20-47): a Tx<PictureSample, PictureSample> with a compute
    context of its own.  This file gives it a body: convert a picture to `outputFormat` at `outputSize`
    on the device — one full-canvas layer through the composite kernels (colour conversion + bilinear
-   scale in one launch) or, without conversion (BGRA -> BGRA, nv12 -> nv12, y420p -> y420p), a separable
-   Lanczos-3 resample (chv_scale_lanczos; a 4:2:0 picture plane by plane).
+   scale in one launch) or a separable Lanczos-3 resample: without conversion (BGRA -> BGRA, nv12 -> nv12,
+   y420p -> y420p; chv_scale_lanczos, a 4:2:0 picture plane by plane), or BGRA / RGBA -> nv12 / y420p through
+   the integer matrix (chv_scale_lanczos_to_yuv).
    It replaces filter.pict.swift when GPGPU_HIP is defined.
 */
 #if GPGPU_HIP
@@ -27,12 +28,14 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                 outputFormat: PixelFormat = .BGRA,
                 scaler: PictureScaler = .bilinear,
                 integerMatrix: Bool = true,
+                colorspace: Int32 = 0,
                 computeContext: ComputeContext? = nil) {
         self.clock = clock
         self.outputSize = outputSize
         self.outputFormat = outputFormat
         self.scaler = scaler
         self.integerMatrix = integerMatrix
+        self.colorspace = colorspace
         do {
             if let context = computeContext {
                 self.context = createComputeContext(sharing: context)
@@ -58,6 +61,11 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                     switch strongSelf.scaler {
                     case .lanczos:
                         let format = strongSelf.outputFormat
+                        let rgbIn = src.pixelFormat() == .BGRA || src.pixelFormat() == .RGBA
+                        if strongSelf.integerMatrix && rgbIn && (format == .nv12 || format == .y420p) {
+                            // (the float full-range matrix has no Lanczos form)
+                            return try scaleLanczosToYuv($0, src: src, target: dst, colorspace: strongSelf.colorspace)
+                        }
                         guard src.pixelFormat() == format, format == .BGRA || format == .nv12 || format == .y420p else {
                             throw ComputeError.notImplemented
                         }
@@ -119,6 +127,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
     let outputFormat: PixelFormat
     let scaler: PictureScaler
     let integerMatrix: Bool
+    let colorspace: Int32      // chv_colorspace of the integer matrix (the Lanczos conversion)
     var context: ComputeContext?
 }
 #endif

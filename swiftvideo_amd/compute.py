@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -727,6 +727,46 @@ class LanczosBatch:
         return ctx
 
 
+def scaleLanczosToYuv(ctx, dst, src, colorspace=cv.CSC_BT601_LIMITED):
+    """Lanczos-3 resize of one BGRA or RGBA plane into the nv12 or y420p picture `dst`, in one launch (chv_scale_lanczos_to_yuv, DESIGN.md
+    section 4.4.2): the codes scaleLanczos would write, luma per pixel and chroma of their 2 x 2 box mean through the integer matrix of
+    `colorspace` — the encoder side's rendition."""
+    d, s = _image_desc(dst), _image_desc(src)
+    if d is None:
+        raise ComputeError(4, "target has no GPU image buffer")
+    if s is None:
+        raise ComputeError(5, "Bad input image")
+    opts = cv.KernelOpts(colorspace=int(colorspace))
+    cv.check(cv.load().chv_scale_lanczos_to_yuv(ctx.handle, C.byref(d), C.byref(s), C.byref(opts)))
+    return ctx
+
+
+class LanczosToYuvBatch:
+    """n conversions of one geometry, one source format, one target format and one colourspace issued as one launch per 83 nv12 or 62
+    y420p pictures (chv_scale_lanczos_to_yuv_batch): the renditions of several streams per tick.  pairs: [(dst PictureSample, src
+    PictureSample)]; the descriptors are built once, `run` can be called every tick."""
+
+    def __init__(self, pairs, colorspace=cv.CSC_BT601_LIMITED):
+        n = len(pairs)
+        self.n = n
+        self._d, self._s = (cv.Image * max(1, n))(), (cv.Image * max(1, n))()
+        self._opts = cv.KernelOpts(colorspace=int(colorspace))
+        self._keep = list(pairs)
+        for i, (dst, src) in enumerate(pairs):
+            d, s = _image_desc(dst), _image_desc(src)
+            if d is None:
+                raise ComputeError(4, "target has no GPU image buffer")
+            if s is None:
+                raise ComputeError(5, "Bad input image")
+            self._d[i], self._s[i] = d, s
+
+    def run(self, ctx):
+        if self.n == 0:          # an empty list is a no-op, as LanczosBatch's
+            return ctx
+        cv.check(cv.load().chv_scale_lanczos_to_yuv_batch(ctx.handle, self._d, self._s, self.n, C.byref(self._opts)))
+        return ctx
+
+
 # ---- pipeline operators -----------------------------------------------------------------------
 class GPUBarrierUpload:
     """Tx<PictureSample, PictureSample>, compute.swift:175-198: owns a context sharing
@@ -766,8 +806,8 @@ class PictureFilter:
     device — the operator the reference sketches and leaves commented out (filter.pict.swift:20-47: same
     constructor shape: a context of its own, sharing the given one).  One full-canvas layer through the
     composite kernels: colour conversion + bilinear scale in one launch (`scaler="bilinear"`, any format
-    pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: no conversion, BGRA -> BGRA, nv12 -> nv12 or
-    y420p -> y420p, a 4:2:0 picture plane by plane).
+    pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p
+    without a conversion, a 4:2:0 picture plane by plane; BGRA or RGBA -> nv12 or y420p through the integer matrix, scaleLanczosToYuv).
     CPU samples are uploaded first; the sample's time stamps, ids and transform state are carried over.
     Results land in a ring of `numberBackingImages` device images like the mixer's (mix.video.swift:148-167)."""
 
@@ -818,7 +858,10 @@ class PictureFilter:
             src = uploadComputePicture(ctx, sample) if sample.bufferType() == "cpu" else sample
             dst = self._backing(sample)
             beginComputePass(ctx)
-            if self.scaler == "lanczos":
+            if self.scaler == "lanczos" and self.integerMatrix and src.pixelFormat() in (PixelFormat.BGRA, PixelFormat.RGBA) \
+                    and self.outputFormat in (PixelFormat.nv12, PixelFormat.y420p):
+                scaleLanczosToYuv(ctx, dst, src, self.colorspace)       # (the float full-range matrix has no Lanczos form)
+            elif self.scaler == "lanczos":
                 if src.pixelFormat() != self.outputFormat or self.outputFormat not in (PixelFormat.BGRA, PixelFormat.nv12, PixelFormat.y420p):
                     raise ComputeError(9, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only")
                 scaleLanczos(ctx, dst, src)

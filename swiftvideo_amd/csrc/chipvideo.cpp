@@ -27,6 +27,7 @@
 #include "geom_cache.h"
 #include "rebind.h"
 #include "lanczos_planar.h"
+#include "lanczos_to_yuv.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -115,6 +116,9 @@ void chv::register_rebind_launcher(RebindLauncher fn) { g_rebind_launcher.store(
 // the planar Lanczos launcher (lanczos_planar.h): null until kernels_lanczos_planar.hip.cpp registers it, and for good in a build without that unit
 static std::atomic<LanczosPlanarLauncher> g_lanczos_planar_launcher{nullptr};
 void chv::register_lanczos_planar_launcher(LanczosPlanarLauncher fn) { g_lanczos_planar_launcher.store(fn, std::memory_order_release); }
+// the same for chv_scale_lanczos_to_yuv (lanczos_to_yuv.h, kernels_lanczos_to_yuv.hip.cpp)
+static std::atomic<LanczosToYuvLauncher> g_lanczos_to_yuv_launcher{nullptr};
+void chv::register_lanczos_to_yuv_launcher(LanczosToYuvLauncher fn) { g_lanczos_to_yuv_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -2372,6 +2376,136 @@ extern "C" int chv_scale_lanczos_batch(chv_context *c, const chv_image *dsts, co
         HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
         (void)hipGetLastError();
         hipError_t e = launch_lanczos(pairs[0], pairs[1], tx->first, tx->weights, tx->taps, ty->first, ty->weights, ty->taps, c->stream, dev, m, tx->stride, tx->first0, ty->stride);
+        if (e != hipSuccess) return hip_fail(e, "lanczos launch");
+    }
+    return CHV_OK;
+}
+
+// ---- chv_scale_lanczos_to_yuv: one BGRA / RGBA plane -> an NV12 or y420p picture ----
+// Pictures per descriptor slot of a batch chunk: a picture's target planes and its source plane must fit one slot together.
+static constexpr int kLanczosToYuvChunkNV12 = 83, kLanczosToYuvChunkY420P = 62;
+static_assert((size_t)kLanczosToYuvChunkNV12 * 3 * sizeof(DPlane) <= kDescSlotBytes && (size_t)(kLanczosToYuvChunkNV12 + 1) * 3 * sizeof(DPlane) > kDescSlotBytes &&
+              (size_t)kLanczosToYuvChunkY420P * 4 * sizeof(DPlane) <= kDescSlotBytes && (size_t)(kLanczosToYuvChunkY420P + 1) * 4 * sizeof(DPlane) > kDescSlotBytes,
+              "a chunk is what fits one descriptor slot (include/chipvideo.h states the counts)");
+
+// DESIGN.md section 4.5's table (the device's copy is kR2Y, pixel_math.hip.h): yoff, then the y, u and v rows over (R, G, B)
+static const int32_t kR2YHost[4][10] = {
+    { 16, 16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681 },   // BT.601 limited
+    { 16, 11966, 40254, 4064, -6596, -22188, 28784, 28784, -26145, -2639 },   // BT.709 limited
+    { 0, 19595, 38470, 7471, -11058, -21710, 32768, 32768, -27439, -5329 },   // BT.601 full
+    { 0, 13933, 46871, 4732, -7509, -25259, 32768, 32768, -29763, -3005 },    // BT.709 full
+};
+
+// (dst, src) of one picture -> its np target planes at out[0 .. np - 1], its source plane at out[np]; every check of plane_to_device
+static int lanczos_to_yuv_planes(chv_context *c, const chv_image *dst, const chv_image *src, int idx, DPlane *out) {
+    const int np = lanczos_planar_planes(dst);
+    if (!np) return fail(CHV_ERR_BAD_TARGET, "Lanczos to YUV: target %d must be nv12 with 2 planes or y420p with 3", idx);
+    if (!src || src->n_planes != 1 || (src->format != CHV_FMT_BGRA && src->format != CHV_FMT_RGBA))
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos to YUV: source %d must be one 4-component plane of format BGRA or RGBA", idx);
+    for (int p = 0; p < np; p++) {
+        int rc = plane_to_device(dst->planes[p], lanczos_planar_comps(dst->format, p), c->device, &out[p], CHV_ERR_BAD_TARGET, "target", p);
+        if (rc) return rc;
+        if (p && (out[p].w != std::max(1, out[0].w / 2) || out[p].h != std::max(1, out[0].h / 2)))
+            return fail(CHV_ERR_BAD_TARGET, "Lanczos to YUV: target %d, plane %d is %dx%d, a %dx%d picture's chroma is %dx%d", idx, p, out[p].w, out[p].h,
+                        out[0].w, out[0].h, std::max(1, out[0].w / 2), std::max(1, out[0].h / 2));
+    }
+    return plane_to_device(src->planes[0], 4, c->device, &out[np], CHV_ERR_BAD_INPUT, "input", 0);
+}
+
+static void lanczos_to_yuv_job(const DPlane *planes, int np, int src_format, const chv_kernel_opts *opts, const LanczosTable &tx, const LanczosTable &ty,
+                               LanczosToYuvJob *job) {
+    memset(job, 0, sizeof *job);
+    job->fx = tx.first; job->wx = tx.weights; job->fy = ty.first; job->wy = ty.weights; job->tx = tx.taps; job->ty = ty.taps;
+    job->n_dst = np;
+    for (int p = 0; p < np; p++) job->dst[p] = planes[p];
+    job->src = planes[np];
+    const int32_t *k = kR2YHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
+    const int r = src_format == CHV_FMT_BGRA ? 2 : 0, b = 2 - r;      // the byte that holds red, blue
+    job->yoff = k[0];
+    job->ky[r] = k[1]; job->ky[1] = k[2]; job->ky[b] = k[3];
+    job->ku[r] = k[4]; job->ku[1] = k[5]; job->ku[b] = k[6];
+    job->kv[r] = k[7]; job->kv[1] = k[8]; job->kv[b] = k[9];
+}
+
+extern "C" int chv_scale_lanczos_to_yuv(chv_context *c, const chv_image *dst, const chv_image *src, const chv_kernel_opts *opts) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    const LanczosToYuvLauncher launcher = g_lanczos_to_yuv_launcher.load(std::memory_order_acquire);
+    DPlane planes[kLanczosToYuvMaxPlanes + 1];
+    DepScope deps;
+    int rc = lanczos_to_yuv_planes(c, dst, src, 0, planes);
+    if (rc) return rc;
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos to YUV kernels");
+    const int np = dst->n_planes;
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    LanczosRef tx, ty;      // held until the launch is enqueued (see LanczosTable)
+    rc = lanczos_table(c, planes[np].w, planes[0].w, &tx);
+    if (rc) return rc;
+    rc = lanczos_table(c, planes[np].h, planes[0].h, &ty);
+    if (rc) return rc;
+    LanczosToYuvJob job;
+    lanczos_to_yuv_job(planes, np, src->format, opts, *tx, *ty, &job);
+    job.batch = nullptr; job.n_pictures = 1;
+    (void)hipGetLastError();
+    hipError_t e = launcher(job, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "lanczos launch");
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_to_yuv_batch(chv_context *c, const chv_image *dsts, const chv_image *srcs, int n, const chv_kernel_opts *opts) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n == 0) return CHV_OK;
+    if (n < 0 || !dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad batch");
+    const LanczosToYuvLauncher launcher = g_lanczos_to_yuv_launcher.load(std::memory_order_acquire);
+    const int np = lanczos_planar_planes(&dsts[0]);
+    if (!np) return fail(CHV_ERR_BAD_TARGET, "Lanczos to YUV: target 0 must be nv12 with 2 planes or y420p with 3");
+    const size_t per = (size_t)np + 1;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    // (one target format and one source format per batch: the list's mistake, not the image's — before anything else is looked at)
+    for (int i = 1; i < n; i++) {
+        if (dsts[i].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "target %d has format %d, the batch began with %d (one target format per batch)", i, dsts[i].format, dsts[0].format);
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the batch began with %d (one source format per batch)", i, srcs[i].format, srcs[0].format);
+    }
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        int rc = lanczos_to_yuv_planes(c, &dsts[i], &srcs[i], i, pi);
+        if (rc) return rc;
+        if (pi[0].w != planes[0].w || pi[0].h != planes[0].h || pi[np].w != planes[np].w || pi[np].h != planes[np].h)
+            return fail(CHV_ERR_INVALID_VALUE, "pair %d: %dx%d -> %dx%d, the batch is %dx%d -> %dx%d (one geometry per batch)", i,
+                        pi[np].w, pi[np].h, pi[0].w, pi[0].h, planes[np].w, planes[np].h, planes[0].w, planes[0].h);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos to YUV kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    LanczosRef tx, ty;
+    rc = lanczos_table(c, planes[np].w, planes[0].w, &tx);
+    if (rc) return rc;
+    rc = lanczos_table(c, planes[np].h, planes[0].h, &ty);
+    if (rc) return rc;
+    LanczosToYuvJob job;
+    lanczos_to_yuv_job(planes.data(), np, srcs[0].format, opts, *tx, *ty, &job);
+    // the planes travel through the pinned, device-mapped descriptor ring (a slot per chunk), like chv_scale_lanczos_batch's pairs
+    const int per_slot = np == 2 ? kLanczosToYuvChunkNV12 : kLanczosToYuvChunkY420P;
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        hipError_t e = launcher(job, c->stream);
         if (e != hipSuccess) return hip_fail(e, "lanczos launch");
     }
     return CHV_OK;

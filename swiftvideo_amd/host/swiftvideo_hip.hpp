@@ -505,6 +505,34 @@ inline ComputeContext scaleLanczos(ComputeContext ctx, const std::vector<std::pa
     return ctx;
 }
 
+// Lanczos-3 resize of one BGRA or RGBA plane into the nv12 or y420p picture `dst`, in one launch (chv_scale_lanczos_to_yuv; DESIGN.md section
+// 4.4.2): the codes scaleLanczos would write, luma per pixel and chroma of their 2 x 2 box mean through the integer matrix of `colorspace` —
+// the encoder side's rendition
+inline ComputeContext scaleLanczosToYuv(ComputeContext ctx, const PictureSample &dst, const PictureSample &src, int colorspace = CHV_CSC_BT601_LIMITED) {
+    chv_image d, s;
+    if (!describe(dst, &d)) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    if (!describe(src, &s)) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    chv_kernel_opts opts{};
+    opts.colorspace = colorspace;
+    check(chv_scale_lanczos_to_yuv(ctx.get(), &d, &s, &opts));
+    return ctx;
+}
+
+// n such conversions of one geometry, one source format, one target format and one colourspace as one launch per chunk
+// (chv_scale_lanczos_to_yuv_batch; 83 pictures into nv12, 62 into y420p): same bytes as n scaleLanczosToYuv calls
+inline ComputeContext scaleLanczosToYuv(ComputeContext ctx, const std::vector<std::pair<PictureSample, PictureSample>> &dstSrcPairs,
+                                        int colorspace = CHV_CSC_BT601_LIMITED) {
+    std::vector<chv_image> d(dstSrcPairs.size()), s(dstSrcPairs.size());
+    for (size_t i = 0; i < dstSrcPairs.size(); i++) {
+        if (!describe(dstSrcPairs[i].first, &d[i])) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+        if (!describe(dstSrcPairs[i].second, &s[i])) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    }
+    chv_kernel_opts opts{};
+    opts.colorspace = colorspace;
+    if (!d.empty()) check(chv_scale_lanczos_to_yuv_batch(ctx.get(), d.data(), s.data(), (int)d.size(), &opts));
+    return ctx;
+}
+
 // Many independent ticks as ONE launch (chv_batch_*): what a host with several mixers / streams on a device
 // (composer.swift:203-224) uses instead of one chv_composite per tick; byte-identical to running them one by one.
 struct Tick { PictureSample target; bool clearFirst = true; std::vector<TickLayer> layers; };
@@ -778,7 +806,8 @@ private:
 // ---- PictureFilter: the Tx<PictureSample, PictureSample> the reference sketches and leaves commented out
 //      (filter.pict.swift:20-47).  Converts a picture to outputFormat at outputSize on the device: one
 //      full-canvas layer through the composite kernels (colour conversion + bilinear scale in one launch),
-//      or a separable Lanczos-3 resample (no conversion: BGRA -> BGRA, nv12 -> nv12, y420p -> y420p).  CPU samples are uploaded first; results land in a
+//      or a separable Lanczos-3 resample (BGRA -> BGRA, nv12 -> nv12, y420p -> y420p without a conversion; BGRA or RGBA -> nv12 or y420p through
+//      the integer matrix, scaleLanczosToYuv).  CPU samples are uploaded first; results land in a
 //      ring of device images like the mixer's (mix.video.swift:148-167). ------------------------------------
 class PictureFilter {
 public:
@@ -804,7 +833,11 @@ public:
         try {
             PictureSample src = sample.bufferType() == BufferType::cpu ? uploadComputePicture(context_, sample) : sample;
             PictureSample dst = getBacking(sample);
-            if (scaler_ == Scaler::lanczos) {
+            const bool rgb = src.pixelFormat() == PixelFormat::BGRA || src.pixelFormat() == PixelFormat::RGBA;
+            if (scaler_ == Scaler::lanczos && integerMatrix && rgb && (format_ == PixelFormat::nv12 || format_ == PixelFormat::y420p)) {
+                // (the float full-range matrix has no Lanczos form)
+                usingContext(context_, [&](ComputeContext c) { return scaleLanczosToYuv(c, dst, src, colorspace_); });
+            } else if (scaler_ == Scaler::lanczos) {
                 if (src.pixelFormat() != format_ || (format_ != PixelFormat::BGRA && format_ != PixelFormat::nv12 && format_ != PixelFormat::y420p))
                     throw ComputeError(CHV_ERR_NOT_IMPLEMENTED, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only");
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczos(c, dst, src); });
