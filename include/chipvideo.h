@@ -71,7 +71,8 @@ int chv_debug_set_switch(const char *name, const char *value);
  * (launches whose layers were pointed at stored tables before their descriptors travelled: batches at creation, lone ticks),
  * "geom_store_batch_hits", "geom_store_builds", "geom_store_bytes", "geom_store_tables"; and "stream_opaque_launches", the launches of
  * tick_bgra_stream that took the opaque-bottom kernels, and "stream_carry_launches", those of them that took the chroma-carry kernels
- * (process-wide).  Unknown name -> CHV_ERR_INVALID_VALUE. */
+ * (process-wide); and "lanczos_ladder_launches", the device launches made by chv_scale_lanczos_to_yuv_ladder (process-wide: one per chunk for a
+ * ladder whose rungs all take one route, two for one with rungs on both).  Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
 /* ---- kernels: `enum ComputeKernel`, compute.swift:49-74 ------------------ */
@@ -447,6 +448,23 @@ int chv_scale_lanczos_to_yuv(chv_context *ctx, const chv_image *dst, const chv_i
  * launched; every other error as above; n == 0 is a no-op.  A chunk is what fits one descriptor slot: 83 pictures into NV12 (3 planes each) or
  * 62 into y420p (4 planes each). */
 int chv_scale_lanczos_to_yuv_batch(chv_context *ctx, const chv_image *dsts, const chv_image *srcs, int n, const chv_kernel_opts *opts);
+/* An encoder LADDER: n_rungs renditions of each of n sources, all of them in one launch per route.  dsts[r * n + i] is
+ * rung r of source i; the call writes the bytes of n_rungs x n calls of chv_scale_lanczos_to_yuv(ctx, &dsts[r * n + i], &srcs[i], opts).
+ * One list, one shape: all sources have one size and one format (BGRA or RGBA), all targets one format (NV12 or y420p), all targets of a rung
+ * one size; rungs may have any sizes (reductions, 1:1, enlargements, the size of another rung).  A violation, n_rungs < 0, n_rungs >
+ * CHV_LADDER_MAX_RUNGS, n < 0 or a NULL list with non-zero counts -> CHV_ERR_INVALID_VALUE; n_rungs == 0 or n == 0 is a no-op.  Every other
+ * error is chv_scale_lanczos_to_yuv's, picture by picture (CHV_ERR_BAD_TARGET, CHV_ERR_BAD_INPUT, CHV_ERR_INVALID_VALUE for a rung the 160 KB
+ * rule refuses, CHV_ERR_NOT_IMPLEMENTED without the kernel unit, after validation).  All or nothing: one refused rung refuses the ladder, nothing
+ * is launched and nothing is written to any rung.  Stream order, upload dependencies and a pass's held work as chv_scale_lanczos_to_yuv_batch.
+ * Launches: the rungs that take the wave-per-strip route leave in one launch, the rungs that take the tile route in at most one more, per chunk.
+ * A chunk is what fits one descriptor slot of CHV_LADDER_SLOT_BYTES, a picture being its n_rungs x planes target planes and its source plane
+ * (stored once) of CHV_LADDER_PLANE_BYTES each: CHV_LADDER_CHUNK(n_rungs, planes) pictures, planes = 2 for NV12 and 3 for y420p.  A longer
+ * list is split along the PICTURES: all rungs of a picture leave in one chunk. */
+#define CHV_LADDER_MAX_RUNGS 8
+#define CHV_LADDER_SLOT_BYTES 5984
+#define CHV_LADDER_PLANE_BYTES 24
+#define CHV_LADDER_CHUNK(n_rungs, planes) (CHV_LADDER_SLOT_BYTES / (((n_rungs) * (planes) + 1) * CHV_LADDER_PLANE_BYTES))
+int chv_scale_lanczos_to_yuv_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, const chv_kernel_opts *opts);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

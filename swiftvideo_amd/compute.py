@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -765,6 +765,45 @@ class LanczosToYuvBatch:
             return ctx
         cv.check(cv.load().chv_scale_lanczos_to_yuv_batch(ctx.handle, self._d, self._s, self.n, C.byref(self._opts)))
         return ctx
+
+
+class LanczosToYuvLadder:
+    """An encoder ladder (chv_scale_lanczos_to_yuv_ladder): every rung of every source in one launch per route — the
+    rungs that take the wave-per-strip route in one, those that take the tile route in at most one more — with the bytes of the single calls.
+    rungs: a list of up to 8 rungs, each the list of that rung's targets, one per source (one size per rung, one format for all); srcs: one
+    sample or a list (one size, one format).  The descriptors are built once, `run` can be called every tick."""
+
+    def __init__(self, rungs, srcs, colorspace=cv.CSC_BT601_LIMITED):
+        srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+        rungs = [list(r) if isinstance(r, (list, tuple)) else [r] for r in rungs]
+        self.n, self.n_rungs = len(srcs), len(rungs)
+        for r, rung in enumerate(rungs):
+            if len(rung) != self.n:
+                raise ComputeError(1, f"rung {r} has {len(rung)} targets for {self.n} sources")
+        self._d, self._s = (cv.Image * max(1, self.n * self.n_rungs))(), (cv.Image * max(1, self.n))()
+        self._opts = cv.KernelOpts(colorspace=int(colorspace))
+        self._keep = (rungs, srcs)
+        for i, src in enumerate(srcs):
+            s = _image_desc(src)
+            if s is None:
+                raise ComputeError(5, "Bad input image")
+            self._s[i] = s
+        for r, rung in enumerate(rungs):
+            for i, dst in enumerate(rung):
+                d = _image_desc(dst)
+                if d is None:
+                    raise ComputeError(4, "target has no GPU image buffer")
+                self._d[r * self.n + i] = d
+
+    def run(self, ctx):
+        cv.check(cv.load().chv_scale_lanczos_to_yuv_ladder(ctx.handle, self._d, self.n_rungs, self._s, self.n, C.byref(self._opts)))
+        return ctx
+
+
+def scaleLanczosToYuvLadder(ctx, rungs, srcs, colorspace=cv.CSC_BT601_LIMITED):
+    """Every rung of an encoder ladder for one or several canvases of one size, all of them in one launch per route
+    (chv_scale_lanczos_to_yuv_ladder): rungs[r][i] receives what scaleLanczosToYuv(ctx, rungs[r][i], srcs[i], colorspace) would write."""
+    return LanczosToYuvLadder(rungs, srcs, colorspace).run(ctx)
 
 
 # ---- pipeline operators -----------------------------------------------------------------------

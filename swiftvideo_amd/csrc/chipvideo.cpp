@@ -28,6 +28,7 @@
 #include "rebind.h"
 #include "lanczos_planar.h"
 #include "lanczos_to_yuv.h"
+#include "lanczos_ladder.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -119,6 +120,9 @@ void chv::register_lanczos_planar_launcher(LanczosPlanarLauncher fn) { g_lanczos
 // the same for chv_scale_lanczos_to_yuv (lanczos_to_yuv.h, kernels_lanczos_to_yuv.hip.cpp)
 static std::atomic<LanczosToYuvLauncher> g_lanczos_to_yuv_launcher{nullptr};
 void chv::register_lanczos_to_yuv_launcher(LanczosToYuvLauncher fn) { g_lanczos_to_yuv_launcher.store(fn, std::memory_order_release); }
+// and for chv_scale_lanczos_to_yuv_ladder (lanczos_ladder.h, kernels_lanczos_ladder.hip.cpp)
+static std::atomic<LanczosLadderLauncher> g_lanczos_ladder_launcher{nullptr};
+void chv::register_lanczos_ladder_launcher(LanczosLadderLauncher fn) { g_lanczos_ladder_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -139,6 +143,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
         if (!strcmp(name, names[i])) { *value = (unsigned long long)geom_store_counter(i); return CHV_OK; }
     if (!strcmp(name, "stream_opaque_launches")) { *value = debug_counters().stream_opaque_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_carry_launches")) { *value = debug_counters().stream_carry_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;
 }
@@ -2412,6 +2417,16 @@ static int lanczos_to_yuv_planes(chv_context *c, const chv_image *dst, const chv
     return plane_to_device(src->planes[0], 4, c->device, &out[np], CHV_ERR_BAD_INPUT, "input", 0);
 }
 
+// section 4.5's rows for `opts` (NULL: BT.601 limited) in the source's BYTE order: the first and third column exchanged for a BGRA source
+static void lanczos_to_yuv_matrix(int src_format, const chv_kernel_opts *opts, int32_t *yoff, int32_t ky[3], int32_t ku[3], int32_t kv[3]) {
+    const int32_t *k = kR2YHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
+    const int r = src_format == CHV_FMT_BGRA ? 2 : 0, b = 2 - r;      // the byte that holds red, blue
+    *yoff = k[0];
+    ky[r] = k[1]; ky[1] = k[2]; ky[b] = k[3];
+    ku[r] = k[4]; ku[1] = k[5]; ku[b] = k[6];
+    kv[r] = k[7]; kv[1] = k[8]; kv[b] = k[9];
+}
+
 static void lanczos_to_yuv_job(const DPlane *planes, int np, int src_format, const chv_kernel_opts *opts, const LanczosTable &tx, const LanczosTable &ty,
                                LanczosToYuvJob *job) {
     memset(job, 0, sizeof *job);
@@ -2419,12 +2434,7 @@ static void lanczos_to_yuv_job(const DPlane *planes, int np, int src_format, con
     job->n_dst = np;
     for (int p = 0; p < np; p++) job->dst[p] = planes[p];
     job->src = planes[np];
-    const int32_t *k = kR2YHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
-    const int r = src_format == CHV_FMT_BGRA ? 2 : 0, b = 2 - r;      // the byte that holds red, blue
-    job->yoff = k[0];
-    job->ky[r] = k[1]; job->ky[1] = k[2]; job->ky[b] = k[3];
-    job->ku[r] = k[4]; job->ku[1] = k[5]; job->ku[b] = k[6];
-    job->kv[r] = k[7]; job->kv[1] = k[8]; job->kv[b] = k[9];
+    lanczos_to_yuv_matrix(src_format, opts, &job->yoff, job->ky, job->ku, job->kv);
 }
 
 extern "C" int chv_scale_lanczos_to_yuv(chv_context *c, const chv_image *dst, const chv_image *src, const chv_kernel_opts *opts) {
@@ -2507,6 +2517,96 @@ extern "C" int chv_scale_lanczos_to_yuv_batch(chv_context *c, const chv_image *d
         (void)hipGetLastError();
         hipError_t e = launcher(job, c->stream);
         if (e != hipSuccess) return hip_fail(e, "lanczos launch");
+    }
+    return CHV_OK;
+}
+
+// ---- chv_scale_lanczos_to_yuv_ladder: every rung of an encoder ladder in one launch per route ----
+// Pictures per descriptor slot of a chunk: a picture's target planes of every rung and its source plane — stored once — must fit one slot
+// together.  include/chipvideo.h states the rule as CHV_LADDER_CHUNK.
+static_assert(CHV_LADDER_SLOT_BYTES == kDescSlotBytes && CHV_LADDER_PLANE_BYTES == sizeof(DPlane), "include/chipvideo.h states the descriptor slot and the plane record");
+static_assert(CHV_LADDER_MAX_RUNGS == kLanczosLadderMaxRungs, "lanczos_ladder.h carries as many rungs as the ABI admits");
+static constexpr int lanczos_ladder_chunk(int n_rungs, int np) { return (int)(kDescSlotBytes / ((size_t)(n_rungs * np + 1) * sizeof(DPlane))); }
+static_assert(lanczos_ladder_chunk(1, 2) == kLanczosToYuvChunkNV12 && lanczos_ladder_chunk(1, 3) == kLanczosToYuvChunkY420P,
+              "a ladder of one rung is chunked like chv_scale_lanczos_to_yuv_batch");
+static_assert(lanczos_ladder_chunk(CHV_LADDER_MAX_RUNGS, 3) >= 1 && lanczos_ladder_chunk(2, 2) == CHV_LADDER_CHUNK(2, 2) && lanczos_ladder_chunk(8, 3) == CHV_LADDER_CHUNK(8, 3),
+              "the longest ladder of the widest format fits one descriptor slot; a chunk is what fits one (include/chipvideo.h states the rule)");
+
+extern "C" int chv_scale_lanczos_to_yuv_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, const chv_kernel_opts *opts) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
+    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
+    if (n_rungs == 0 || n == 0) return CHV_OK;
+    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    const LanczosLadderLauncher launcher = g_lanczos_ladder_launcher.load(std::memory_order_acquire);
+    const int np = lanczos_planar_planes(&dsts[0]);
+    if (!np) return fail(CHV_ERR_BAD_TARGET, "Lanczos to YUV: target 0 must be nv12 with 2 planes or y420p with 3");
+    // (one target format and one source format per ladder: the list's mistake, not the image's — before anything else is looked at)
+    for (int k = 1; k < n_rungs * n; k++)
+        if (dsts[k].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
+    for (int i = 1; i < n; i++)
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    // a picture's descriptor: the np target planes of rung 0, of rung 1, ..., then the source plane
+    const size_t per = (size_t)n_rungs * np + 1;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        for (int r = 0; r < n_rungs; r++) {
+            DPlane one[kLanczosToYuvMaxPlanes + 1];
+            int rc = lanczos_to_yuv_planes(c, &dsts[(size_t)r * n + i], &srcs[i], r * n + i, one);
+            if (rc) return rc;
+            for (int p = 0; p < np; p++) pi[r * np + p] = one[p];
+            pi[per - 1] = one[np];
+            if (one[0].w != planes[r * np].w || one[0].h != planes[r * np].h)
+                return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, one[0].w, one[0].h,
+                            planes[r * np].w, planes[r * np].h);
+        }
+        if (pi[per - 1].w != planes[per - 1].w || pi[per - 1].h != planes[per - 1].h)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, pi[per - 1].w, pi[per - 1].h,
+                        planes[per - 1].w, planes[per - 1].h);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos ladder kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    // two tables per rung, from the shared cache (rungs of one geometry share theirs); held until the last launch is enqueued
+    LanczosRef refs[2 * CHV_LADDER_MAX_RUNGS];
+    LanczosLadderJob job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs; job.n_dst = np;
+    job.src_w = planes[per - 1].w; job.src_h = planes[per - 1].h;
+    for (int r = 0; r < n_rungs; r++) {
+        const DPlane &d = planes[r * np];
+        rc = lanczos_table(c, job.src_w, d.w, &refs[2 * r]);
+        if (rc) return rc;
+        rc = lanczos_table(c, job.src_h, d.h, &refs[2 * r + 1]);
+        if (rc) return rc;
+        const LanczosTable &tx = *refs[2 * r], &ty = *refs[2 * r + 1];
+        job.rung[r] = LanczosLadderRung{ tx.first, tx.weights, ty.first, ty.weights, tx.taps, ty.taps, d.w, d.h };
+    }
+    lanczos_to_yuv_matrix(srcs[0].format, opts, &job.yoff, job.ky, job.ku, job.kv);
+    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES, so
+    // all rungs of a picture leave in one chunk
+    const int per_slot = lanczos_ladder_chunk(n_rungs, np);
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        if (e != hipSuccess) return hip_fail(e, "lanczos ladder launch");
     }
     return CHV_OK;
 }

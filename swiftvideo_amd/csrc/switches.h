@@ -46,6 +46,7 @@ Switches &switches();                    // (chipvideo.cpp; initialised from the
 struct DebugCounters {
     std::atomic<unsigned long long> stream_opaque_launches{0};       // launches of tick_bgra_stream that took the opaque-bottom kernels
     std::atomic<unsigned long long> stream_carry_launches{0};        // ... of which: the chroma-carry kernels (kernels_stream_carry.hip.cpp)
+    std::atomic<unsigned long long> lanczos_ladder_launches{0};      // device launches made by chv_scale_lanczos_to_yuv_ladder
 };
 DebugCounters &debug_counters();
 
