@@ -90,19 +90,20 @@ static int parse_switch(const char *name, const char *value, int *out) {
     if (n == "CHV_STREAM_OPAQUE") { *out = v == "0" ? 0 : 1; return 12; }
     if (n == "CHV_STREAM_CARRY") { *out = v == "0" ? 0 : 1; return 14; }
     if (n == "CHV_REBIND") { *out = v == "scatter" ? 1 : v == "copy" ? 2 : 0; return 13; }
+    if (n == "CHV_STREAM_F32TAPS") { *out = v == "0" ? 0 : 1; return 15; }
     return -1;
 }
 static void store_switch(Switches &s, int which, int val) {
-    std::atomic<int> *slots[15] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
-                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows, &s.stream_opaque, &s.rebind, &s.stream_carry };
+    std::atomic<int> *slots[16] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
+                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows, &s.stream_opaque, &s.rebind, &s.stream_carry, &s.stream_f32taps };
     slots[which]->store(val, std::memory_order_relaxed);
 }
 Switches &chv::switches() {
     static Switches s;
     static std::once_flag once;
     std::call_once(once, [] {
-        static const char *const names[15] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
-                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS", "CHV_STREAM_OPAQUE", "CHV_REBIND", "CHV_STREAM_CARRY" };
+        static const char *const names[16] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
+                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS", "CHV_STREAM_OPAQUE", "CHV_REBIND", "CHV_STREAM_CARRY", "CHV_STREAM_F32TAPS" };
         for (const char *n : names) {
             const char *v = getenv(n);
             int val = 0, which = v ? parse_switch(n, v, &val) : -1;
@@ -132,7 +133,7 @@ extern "C" int chv_debug_set_switch(const char *name, const char *value) {
     Switches &s = switches();                     // (environment first, so that a later first use cannot overwrite this)
     const int which = parse_switch(name, value, &val);
     if (which < 0) { g_detail_set("unknown switch"); return CHV_ERR_INVALID_VALUE; }
-    if (!value || !*value) val = (which == 4 || which == 6 || which == 7 || which == 8 || which == 9 || which == 10 || which == 12 || which == 14) ? 1 : 0;      // empty / NULL: back to "the library decides"
+    if (!value || !*value) val = (which == 4 || which == 6 || which == 7 || which == 8 || which == 9 || which == 10 || which == 12 || which == 14 || which == 15) ? 1 : 0;      // empty / NULL: back to "the library decides"
     store_switch(s, which, val);
     return CHV_OK;
 }
@@ -143,6 +144,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
         if (!strcmp(name, names[i])) { *value = (unsigned long long)geom_store_counter(i); return CHV_OK; }
     if (!strcmp(name, "stream_opaque_launches")) { *value = debug_counters().stream_opaque_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_carry_launches")) { *value = debug_counters().stream_carry_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "stream_f32tap_launches")) { *value = debug_counters().stream_f32tap_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;

@@ -265,4 +265,53 @@ hipError_t launch_selftest(float *out_f, const float *in_f, uint8_t *out_c, cons
     return hipGetLastError();
 }
 
+// The f32-tap identity of tick_bgra_stream_cd (cs_mix_d, pixel_math.hip.h) on the device, item by item: column fraction xa[i], row fraction ya[i]
+// (weights formed as stream_body forms them), four tap bytes, a conversion constant m[i].  out[3i ..] = the bits of the biased sample through
+// the reference chain on converted floats, through tap_h / cs_mix_h (the sibling kernels' form) and through cs_mix_d + the fused un-scaling.
+__global__ void selftest_f32_taps_kernel(const float *xa, const float *ya, const uint32_t *taps, const float *m, uint32_t *out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = xa[i], b = ya[i], ib = 1.0f - b;
+    const uint32_t t00 = taps[4 * i], t10 = taps[4 * i + 1], t01 = taps[4 * i + 2], t11 = taps[4 * i + 3];
+    auto weights = [&](float scale, float &w00, float &w10, float &w01, float &w11) {
+        const float ia = (1.0f - a) * scale, sa = a * scale;
+        w00 = ia * ib; w10 = sa * ib; w01 = ia * b; w11 = sa * b;
+    };
+    float w00, w10, w01, w11;
+    weights(1.0f, w00, w10, w01, w11);
+    out[3 * i] = __float_as_uint(cs_mix(w00, w10, w01, w11, (float)t00, (float)t10, (float)t01, (float)t11) + m[i]);
+    weights(kTapScale, w00, w10, w01, w11);
+    out[3 * i + 1] = __float_as_uint(cs_mix_h(w00, w10, w01, w11, tap_h(t00), tap_h(t10), tap_h(t01), tap_h(t11)) + m[i]);
+    weights(kTapScaleD, w00, w10, w01, w11);
+    float unscale = kTapUnscaleD;
+    asm volatile("" : "+v"(unscale));
+    out[3 * i + 2] = __float_as_uint(__builtin_fmaf(cs_mix_d(w00, w10, w01, w11, t00, t10, t01, t11), unscale, m[i]));
+}
+
 }  // namespace chv
+
+// exported beside the other self-tests (bound by tests/test_gpu_stream_f32taps.py only; not part of chipvideo.h): host arrays in, 3n words out,
+// on the current device; returns the HIP error code (0: ran)
+extern "C" int chv_selftest_f32_taps(const float *xa, const float *ya, const uint32_t *taps /*4n*/, const float *m, uint32_t *out /*3n*/, int n) {
+    if (!xa || !ya || !taps || !m || !out || n <= 0) return (int)hipErrorInvalidValue;
+    float *d_x = nullptr, *d_y = nullptr, *d_m = nullptr;
+    uint32_t *d_t = nullptr, *d_o = nullptr;
+    const size_t f = (size_t)n * sizeof(float);
+    hipError_t e = hipMalloc((void **)&d_x, f);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_y, f);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_m, f);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_t, 4 * f);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_o, 3 * f);
+    if (e == hipSuccess) e = hipMemcpy(d_x, xa, f, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_y, ya, f, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_m, m, f, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_t, taps, 4 * f, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(chv::selftest_f32_taps_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, d_y, d_t, d_m, d_o, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_o, 3 * f, hipMemcpyDeviceToHost);
+    (void)hipFree(d_x); (void)hipFree(d_y); (void)hipFree(d_m); (void)hipFree(d_t); (void)hipFree(d_o);
+    return (int)e;
+}

@@ -1,6 +1,6 @@
 // kernels_stream_body.hip.inc — stream_body, the device code of the tick_bgra_stream kernels, and what it is built with: included by
 // kernels_stream.hip.cpp (the 32 kernels of every eligible launch), kernels_stream_opq.hip.cpp (the opaque-bottom kernels) and
-// kernels_stream_carry.hip.cpp (the chroma-carry kernels), each of which instantiates its own __global__ wrappers.  The kernel's description is at the top of kernels_stream.hip.cpp.
+// kernels_stream_carry.hip.cpp (the chroma-carry kernels) and kernels_stream_dn.hip.cpp (their f32-tap form), each of which instantiates its own __global__ wrappers.  The kernel's description is at the top of kernels_stream.hip.cpp.
 #pragma once
 #include "wave_common.hip.h"
 #include "switches.h"
@@ -169,7 +169,10 @@ CHV_DEV void st_carry_wait(StLuma &t, StCarry<NL> &even, StCarry<NL> &odd) {
 // cleared canvas its blend RN(code x 1) is the code it already holds as a clamped 16.16 sum, so the layer computes no blend, and layer 1
 // takes that sum times its 1 - opacity through one v_fma_mix_f32 per channel (see `ial24`).
 // CRY: the chroma taps are carried down the lane from row to row (StCarry above; kernels_stream_carry.hip.cpp: OPQ batch kernels of NV12 sources)
-template <int NL, bool ONE, bool PL, bool ABS, bool OPQ = false, bool CRY = false>
+// DN: the taps of the carry form enter full-rate v_fma_f32 / v_fmac_f32 as binary32 denormals instead of v_fma_mix_f32 as binary16 ones
+// (cs_mix_d, pixel_math.hip.h; kernels_stream_dn.hip.cpp): the column weights carry 2^127 where they carry kTapScale, the samples leave the
+// taps scaled by 2^-22 and the 2^22 rides on the add that converts them (yuv_to_bgr_fixed_absorbed_d).  Same bytes; the blend is untouched.
+template <int NL, bool ONE, bool PL, bool ABS, bool OPQ = false, bool CRY = false, bool DN = false>
 CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int n_ticks, int strips_x, int chunks_y, int rows_per_chunk) {
     // ST_WAVES independent waves per block, on neighbouring strips (no barrier anywhere): their source windows overlap by a vector or two,
     // and waves of one block start together on one CU — the shared lines are fetched once (HBM traffic 1.47x -> see profiles/r03_notes.md)
@@ -185,6 +188,7 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
     const uint32_t lds0 = (uint32_t)(size_t)lds;                  // LDS byte address of the rings (the DMA's M0)
     static_assert(!OPQ || (NL >= 2 && ABS && CHV_STREAM_PMIX), "the opaque-bottom form: two layers or more, absorbed matrices, binary16 blend inputs");
     static_assert(!CRY || (OPQ && !PL && !ONE && !(CHV_ST_ABL & 4)), "the chroma-carry form: opaque-bottom batch kernels of NV12 sources");
+    static_assert(!DN || CRY, "the f32-tap form: the chroma-carry kernels");
     const int lane = threadIdx.x & 63;
     // XCD-aware numbering: block b runs on XCD b % 8; an XCD owns a contiguous range of (tick, chunk, group of ST_WAVES strips)
     const int groups_x = (strips_x + ST_WAVES - 1) / ST_WAVES;
@@ -229,7 +233,9 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
     // again with two more vector instructions per tap pair: every tap its own byte read is the cheaper form here, r03_notes.md section 2)
     int oc0v = oc0, oc1v = oc1;
     asm("" : "+v"(oc0v), "+v"(oc1v));
-    const float iya = (1.0f - cya) * kTapScale, ya = cya * kTapScale, ica = (1.0f - cca) * kTapScale, ca = cca * kTapScale;
+    // (DN: kTapScaleD, the largest power of two — see cs_mix_d for the overflow and underflow bounds)
+    constexpr float kColScale = DN ? kTapScaleD : kTapScale;
+    const float iya = (1.0f - cya) * kColScale, ya = cya * kColScale, ica = (1.0f - cca) * kColScale, ca = cca * kColScale;
     const bool lane_pic = cfl == AX_ALL && x < T.W;
     // 16-byte vectors of a ring row that some tap of the strip can read (the last lane has the largest offsets): the rest is not requested
     const int nvecY = (__builtin_amdgcn_readlane(oy1, 63) >> 4) + 1, nvecC = ((__builtin_amdgcn_readlane(oc1, 63) + BPC - 1) >> 4) + 1;
@@ -280,6 +286,10 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
     uint32_t pending = 0u;                                        // the previous row's pixel, stored after this row's wait
     uint32_t alpha_word = 0xFF000000u;                            // img_clear_bgra's pixel; the word the colour bytes are packed into
     asm volatile("" : "+v"(alpha_word));
+    // DN: 2^22, what takes the taps' 2^-22 out again, in a vector register of its own like alpha_word and nrb: the fused multiply-add that
+    // converts a sample reads its one scalar operand for the layer's bias
+    [[maybe_unused]] float unscale = kTapUnscaleD;
+    if constexpr (DN) asm volatile("" : "+v"(unscale));
     int issued = 0, seqY = 0, seqC = 0;                           // load instructions issued so far; the count right after the newest luma / chroma batch
     int nextY = 0, nextC = 0, landY = 0, landC = 0, baseY = 0, baseC = 0;      // ring state: rows below next* are requested, below land* have arrived
     // CRY: the carried chroma bytes — ring rows (row - baseC) & 1 == 0 in `cset[0]`, the others in `cset[1]` — and the source row each holds
@@ -433,11 +443,19 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
                         else if constexpr (l >= 1) st_luma_wait<0>(lum[l & 1]);
                         const StLuma &t = lum[l & 1];
                         const uint32_t *ct = cset[TOP].c[l], *cb_ = cset[1 - TOP].c[l];
+                        int32_t cb, cg, cr;
+                        if constexpr (DN) {
+                            // (the registers the byte reads filled ARE the operands: b x 2^-149; fy, fu, fv are the samples x 2^-22)
+                            const float fy = cs_mix_d(w00, w10, w01, w11, t.y00, t.y10, t.y01, t.y11);
+                            const float fu = cs_mix_d(c00, c10, c01, c11, ct[0], ct[1], cb_[0], cb_[1]);
+                            const float fv = cs_mix_d(c00, c10, c01, c11, ct[2], ct[3], cb_[2], cb_[3]);
+                            yuv_to_bgr_fixed_absorbed_d(csc[l], unscale, fy, fu, fv, cb, cg, cr);
+                        } else {
                         const float fy = cs_mix_h(w00, w10, w01, w11, tap_h(t.y00), tap_h(t.y10), tap_h(t.y01), tap_h(t.y11));
                         const float fu = cs_mix_h(c00, c10, c01, c11, tap_h(ct[0]), tap_h(ct[1]), tap_h(cb_[0]), tap_h(cb_[1]));
                         const float fv = cs_mix_h(c00, c10, c01, c11, tap_h(ct[2]), tap_h(ct[3]), tap_h(cb_[2]), tap_h(cb_[3]));
-                        int32_t cb, cg, cr;
                         yuv_to_bgr_fixed_absorbed(csc[l], fy, fu, fv, cb, cg, cr);
+                        }
                         const float a24 = al24[l];
                         if constexpr (l == 0) {
                             q0 = cb; q1 = cg; q2 = cr;

@@ -12,6 +12,9 @@ namespace chv {
 // kernels_stream_carry.hip.cpp: the chroma-carry kernels (NV12 batches of 2 - 4 layers), same grid, LDS and arguments
 hipError_t launch_bgra_stream_carry(int nl, const DTick *ticks, const DLayer *layers, int n_ticks, dim3 grid, size_t lds, int strips_x, int chunks_y, int rows,
                                     hipStream_t stream);
+// kernels_stream_dn.hip.cpp: the same kernels with their taps on the f32 multiplier (CHV_STREAM_F32TAPS)
+hipError_t launch_bgra_stream_f32taps(int nl, const DTick *ticks, const DLayer *layers, int n_ticks, dim3 grid, size_t lds, int strips_x, int chunks_y, int rows,
+                                      hipStream_t stream);
 
 template <int NL, bool PL, bool ABS>
 __global__ __launch_bounds__(64 * ST_WAVES, CHV_STREAM_WAVES) void tick_bgra_stream_ob(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int n_ticks,
@@ -31,8 +34,11 @@ hipError_t launch_bgra_stream_opaque(const DTick *ticks_host, const DLayer *laye
     if (nl < 2 || nl > 4) return hipErrorInvalidValue;
     // NV12 batches whose chroma advances by at most one row per canvas row: the chroma taps carried from row to row (stream_select.h)
     if (stream_chroma_carry(ticks_host, layers_host, n_ticks, planar, !ticks, switches().stream_carry.load(std::memory_order_relaxed))) {
-        const hipError_t err = launch_bgra_stream_carry(nl, ticks, layers, n_ticks, grid, lds, strips_x, chunks_y, rows, stream);
+        const bool f32taps = switches().stream_f32taps.load(std::memory_order_relaxed) != 0;
+        const hipError_t err = f32taps ? launch_bgra_stream_f32taps(nl, ticks, layers, n_ticks, grid, lds, strips_x, chunks_y, rows, stream)
+                                       : launch_bgra_stream_carry(nl, ticks, layers, n_ticks, grid, lds, strips_x, chunks_y, rows, stream);
         if (err == hipSuccess) debug_counters().stream_carry_launches.fetch_add(1, std::memory_order_relaxed);
+        if (err == hipSuccess && f32taps) debug_counters().stream_f32tap_launches.fetch_add(1, std::memory_order_relaxed);
         return err;
     }
     auto go = [&](auto tag, auto pl) {

@@ -267,6 +267,27 @@ CHV_DEV chv_half tap_h(const uint8_t *p) { return tap_h((uint32_t)*p); }
 CHV_DEV float cs_mix_h(float w00, float w10, float w01, float w11, chv_half t00, chv_half t10, chv_half t01, chv_half t11) {
     return __builtin_fmaf(w11, (float)t11, __builtin_fmaf(w01, (float)t01, __builtin_fmaf(w10, (float)t10, __builtin_fmaf(w00, (float)t00, 0.0f))));
 }
+// ---- the same taps through the FULL-RATE f32 multiplier ---------------------------------------------------------------------------------
+// The zero-extended byte is also the binary32 denormal b * 2^-149 — the whole register ds_read_u8 returns — so a tap can be a plain
+// v_fma_f32 / v_fmac_f32 (1.1 ns per wave on a SIMD where v_fma_mix_f32 costs 1.8; profiles/f32_denormal_taps_notes.md).  With B = bits(b)
+// and W = w * 2^127
+//     fma(W, B, ACC * 2^-22)  =  RN(w b 2^-22 + ACC 2^-22)  =  2^-22 * fmaf(w, (float)b, ACC)                    bit for bit:
+// every scaling is a power of two, so each rounding sees the reference's significand as long as nothing overflows or underflows.
+//   overflow:  a weight is a product of two factors in [0, 1]: W <= 2^127 = 0x7F000000 < FLT_MAX, and a scaled sum is below 256 * 2^-22;
+//   underflow: a scaled partial sum is 2^-22 times the reference's, so it is normal — and rounds as the reference's does — wherever
+//              the reference's is zero or at least 2^-104; the weights are fractions of tap positions (multiples of 2^-24 at the very least
+//              once a coordinate reaches 1, times a second such fraction) and a nonzero sum of them times a byte stays above about
+//              2^-50: the argument that keeps w * kTapScale exact in tap_h's form, with fifty binades to spare.
+// The product is exact inside the FMA (no denormal flush: .amdhsa_float_denorm_mode_32 3, asserted by tests/test_stream_dn_contract.py).
+// The 2^-22 leaves on the add that already follows every sample (yuv_to_bgr_fixed_absorbed_d below): fma(S, 2^22, m) rounds the real number
+// s + m once, as s + m does.  tests/cpp/test_f32_taps.cpp checks the identity on the CPU, tests/test_gpu_stream_f32taps.py on the device.
+constexpr float kTapScaleD = 0x1p127f;         // on the column weights (in [0, 1]: no overflow)
+constexpr float kTapUnscaleD = 0x1p22f;        // 2^127 * 2^-149 = 2^-22 on every sample
+// cs_mix with the four weights already multiplied by kTapScaleD and the taps as the registers the byte reads returned: the samples * 2^-22
+CHV_DEV float cs_mix_d(float w00, float w10, float w01, float w11, uint32_t t00, uint32_t t10, uint32_t t01, uint32_t t11) {
+    return __builtin_fmaf(w11, __uint_as_float(t11), __builtin_fmaf(w01, __uint_as_float(t01), __builtin_fmaf(w10, __uint_as_float(t10),
+                          __builtin_fmaf(w00, __uint_as_float(t00), 0.0f))));
+}
 
 // RTE of a code-scale value known to lie in [0, 255 + a few ulp] and not NaN (a convex combination
 // of codes), through the float adder: returns the raw bits 0x4B400000 + rint(v)
@@ -441,6 +462,17 @@ CHV_DEV CscAbsorbed csc_fold_absorbed(int csc) { return kCscAbsorbed[csc & 3]; }
 // v_cvt_f32_ubyte2 + v_fmac_f32 were two.
 CHV_DEV void yuv_to_bgr_fixed_absorbed(const CscAbsorbed &k, float fy, float fu, float fv, int32_t &cb, int32_t &cg, int32_t &cr) {
     const int y = (int)__float_as_uint(fy + k.my), u = (int)__float_as_uint(fu + k.mu), v = (int)__float_as_uint(fv + k.mv);
+    const int32_t t = __mul24(y, k.cy);
+    const int32_t r = mad24_uniform(v, k.crv, t);
+    const int32_t g = mad24_uniform(v, k.ncgv, mad24_uniform(u, k.ncgu, t)) + k.kg;
+    const int32_t b = mad24_uniform(u, k.cbu, t);
+    cb = min(max(b, 0), 0xFFFFFF); cg = min(max(g, 0), 0xFFFFFF); cr = min(max(r, 0), 0xFFFFFF);
+}
+// the same on samples that arrive scaled by 2^-22 (cs_mix_d): `unscale` is kTapUnscaleD in a vector register, the bias the instruction's one
+// scalar operand — fma(fS, 2^22, m) is the same real number f + m into the same single rounding
+CHV_DEV void yuv_to_bgr_fixed_absorbed_d(const CscAbsorbed &k, float unscale, float fyS, float fuS, float fvS, int32_t &cb, int32_t &cg, int32_t &cr) {
+    const int y = (int)__float_as_uint(__builtin_fmaf(fyS, unscale, k.my)), u = (int)__float_as_uint(__builtin_fmaf(fuS, unscale, k.mu)),
+              v = (int)__float_as_uint(__builtin_fmaf(fvS, unscale, k.mv));
     const int32_t t = __mul24(y, k.cy);
     const int32_t r = mad24_uniform(v, k.crv, t);
     const int32_t g = mad24_uniform(v, k.ncgv, mad24_uniform(u, k.ncgu, t)) + k.kg;

@@ -2,7 +2,7 @@
 //
 // The environment is read ONCE, at the first use in the process (getenv on a hot path is undefined behaviour next to a
 // setenv in another thread, and the mixer and uploader threads run concurrently): CHV_FORCE_GENERAL, CHV_BGRA_PATH,
-// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE, CHV_STREAM_CARRY, CHV_REBIND.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
+// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE, CHV_STREAM_CARRY, CHV_STREAM_F32TAPS, CHV_REBIND.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
 // never through the environment.  Every value is an atomic int; 0 = "the library decides".
 #pragma once
 #include <atomic>
@@ -35,6 +35,9 @@ struct Switches {
     std::atomic<int> stream_carry{1};    // CHV_STREAM_CARRY: 0 opaque-bottom launches keep the kernels that read every chroma tap on every row (A/B and parity
                                          // tests); 1 (default) NV12 batches whose chroma advances by at most one row per canvas row take the chroma-carry
                                          // kernels (kernels_stream_carry.hip.cpp; stream_select.h)
+    std::atomic<int> stream_f32taps{1};  // CHV_STREAM_F32TAPS: 0 chroma-carry launches keep the kernels whose taps are v_fma_mix_f32 (A/B and parity tests); 1 (default)
+                                         // they take the kernels whose taps are f32 multiply-adds on binary32 denormals (kernels_stream_dn.hip.cpp;
+                                         // profiles/f32_denormal_taps_notes.md)
     std::atomic<int> rebind{0};          // CHV_REBIND, how chv_batch_rebind sends the new plane addresses: scatter (1) the scatter kernel (kernels_rebind.hip.cpp)
                                          // wherever the batch has a pooled block and the unit is linked; copy (2) the whole descriptor block again (A/B, and
                                          // the only way without them); 0 (default) the library decides (profiles/batch_rebind_notes.md)
@@ -46,6 +49,7 @@ Switches &switches();                    // (chipvideo.cpp; initialised from the
 struct DebugCounters {
     std::atomic<unsigned long long> stream_opaque_launches{0};       // launches of tick_bgra_stream that took the opaque-bottom kernels
     std::atomic<unsigned long long> stream_carry_launches{0};        // ... of which: the chroma-carry kernels (kernels_stream_carry.hip.cpp)
+    std::atomic<unsigned long long> stream_f32tap_launches{0};       // ... of which: the f32-tap kernels (kernels_stream_dn.hip.cpp)
     std::atomic<unsigned long long> lanczos_ladder_launches{0};      // device launches made by chv_scale_lanczos_to_yuv_ladder
 };
 DebugCounters &debug_counters();

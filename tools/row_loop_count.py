@@ -66,11 +66,12 @@ def _target(ins, op, args):
     return ins[0][0] + int(m.group(1), 16) if m else None
 
 
-def row_loop_copies(ins):
+def row_loop_copies(ins, min_mix=12):
     """The row loop of a kernel whose row exists in more than one copy behind a uniform branch (the chroma-carry kernels: "the top tap row
     is the even set" / "the odd set"): a list with, per copy, the instructions a row that takes THAT copy passes through — the loop
     without the other copies.  A copy is the range a forward branch inside the loop jumps over, if that range holds the arithmetic of
-    a row's layers (twelve v_fma_mix_f32 or more) and no smaller such range lies inside it: hipcc lays `if (p) A else B` out as "skip A
+    a row's layers (`min_mix` v_fma_mix_f32 or more: twelve by default; the f32-tap kernels of kernels_stream_dn.hip.o keep three per layer) and no
+    smaller such range lies inside it: hipcc lays `if (p) A else B` out as "skip A
     unless p; A; skip B if p; B" or as "branch to B; A; jump over B; B", and both jump over each copy once.  A kernel with one copy
     gives a list of one: row_loop(ins)."""
     loop = row_loop(ins)
@@ -81,7 +82,7 @@ def row_loop_copies(ins):
     spans = []
     for a, op, args in loop:
         t = _target(ins, op, args)
-        if t is not None and a < t <= hi + 4 and sum(1 for m in mix if a < m < t) >= 12:
+        if t is not None and a < t <= hi + 4 and sum(1 for m in mix if a < m < t) >= min_mix:
             spans.append((a, t))
     spans = sorted(set(s for s in spans if not any(o != s and s[0] <= o[0] and o[1] <= s[1] for o in spans)))
     # (two branches may jump over one copy from different places: keep the widest of those that share their end)
@@ -123,7 +124,7 @@ def count(obj, fragment=""):
         if fragment not in n:
             continue
         out[n] = classes(row_loop(i))
-        copies = row_loop_copies(i)
+        copies = row_loop_copies(i, 6 if "tick_bgra_stream_cd" in n else 12)
         for k, c in enumerate(copies if len(copies) > 1 else []):
             out[f"{n[:40]} [copy {k + 1} of {len(copies)}]"] = classes(c)
     return out

@@ -59,6 +59,9 @@
 #define I_MED3I(d)    "v_med3_i32 " #d ", " #d ", 0, %10"
 #define I_CVTFI(d)    "v_cvt_f32_i32 " #d ", " #d
 #define I_ALIGNBIT(d) "v_alignbit_b32 " #d ", " #d ", %10, 16"
+// a tap as the kernels issue it: acc += sample x weight, the sample in %10, the weight in %8 (OP 60 .. 63 set them: see bench)
+#define I_FMATAP(d)   "v_fma_f32 " #d ", %10, %8, " #d
+#define I_FMACTAP(d)  "v_fmac_f32 " #d ", %10, %8"
 // whole packs of three 16.16 sums (registers r0..r2 / r4..r6) into a BGRA word, two pixels per group of (5 | 5 | 3) x 2 instructions
 #define PACK_MED3 asm volatile("v_med3_i32 %0, %0, 0, %10\n v_med3_i32 %1, %1, 0, %10\n v_med3_i32 %2, %2, 0, %10\n v_perm_b32 %3, %1, %0, %10\n v_perm_b32 %3, %2, %3, %10\n" \
     "v_med3_i32 %4, %4, 0, %10\n v_med3_i32 %5, %5, 0, %10\n v_med3_i32 %6, %6, 0, %10\n v_perm_b32 %7, %5, %4, %10\n v_perm_b32 %7, %6, %7, %10" \
@@ -86,6 +89,17 @@ __global__ __launch_bounds__(256) void bench(uint32_t *out, int iters, float see
     float b0 = seed * 0.999f, b1 = seed * 1e-3f;
     uint32_t i2 = 0x00550033u + threadIdx.x;
     uint32_t r0 = threadIdx.x + 1, r1 = r0 * 3, r2 = r0 * 5, r3 = r0 * 7, r4 = r0 * 11, r5 = r0 * 13, r6 = r0 * 17, r7 = r0 * 19;
+    if (OP >= 60 && OP <= 63) {
+        // the tap forms: the sample is a byte 1 .. 255, as the float (OP 60, 62: a normal operand, weight w x 2^-22) or as its RAW BITS, the
+        // binary32 denormal b x 2^-149 that ds_read_u8 leaves in a register (OP 61, 63: weight w x 2^127) — the same products, b x w x 2^-22,
+        // onto the same normal accumulators ((lane + 1) x 2^-22 .. below 1 after every iteration)
+        const uint32_t byte = 1u + (threadIdx.x * 37u) % 255u;
+        const bool dn = OP == 61 || OP == 63;
+        i2 = dn ? byte : __float_as_uint((float)byte);
+        b0 = dn ? seed * 0x1p126f : seed * 0x1p-23f;                // w = seed / 2 = 0.75
+        r0 = __float_as_uint((float)(threadIdx.x + 1) * 0x1p-22f);
+        r1 = r0 + 3; r2 = r0 + 5; r3 = r0 + 7; r4 = r0 + 11; r5 = r0 + 13; r6 = r0 + 17; r7 = r0 + 19;
+    }
     for (int it = 0; it < iters; it++) {
         if (OP == 0) { REP16(G8(I_FMA)) }
         if (OP == 1) { REP16(G8(I_MUL)) }
@@ -132,11 +146,50 @@ __global__ __launch_bounds__(256) void bench(uint32_t *out, int iters, float see
         if (OP == 54) { REP16(PACK_MED3) }
         if (OP == 55) { REP16(PACK_SATPK) }
         if (OP == 56) { REP16(PACK_ASHR) }
+        if (OP == 60 || OP == 61) { REP16(G8(I_FMATAP)) }
+        if (OP == 62 || OP == 63) { REP16(G8(I_FMACTAP)) }
         if (OP == 40) { REP16(MIX_FMA_CVT) }
         if (OP == 41) { REP16(MIX_FMA_MAD) }
         if (OP == 42) { REP16(MIX_FMA_SALU) }
     }
     if ((r0 ^ r1 ^ r2 ^ r3 ^ r4 ^ r5 ^ r6 ^ r7) == 0x12345678u) out[0] = 1;  // keep results live
+}
+
+// WHY the tap form is slow where `v_fmac_f32 d, b0, b1` is fast: the sample's register (named here: v20 shares v22's parity and, of four banks,
+// neither's; v21 is the weight's neighbour, as b0 / b1 are) against the sample's DATA (one value in every lane and wave, or a byte per lane).
+// MODE bit 0: the sample in v20 (else v21); bit 1: a byte per lane (else 77 everywhere); bit 2: as raw bits, a denormal; the weight in v22.
+#define T8(S) asm volatile("v_fmac_f32 %0, " S ", v22\nv_fmac_f32 %1, " S ", v22\nv_fmac_f32 %2, " S ", v22\nv_fmac_f32 %3, " S ", v22\n" \
+    "v_fmac_f32 %4, " S ", v22\nv_fmac_f32 %5, " S ", v22\nv_fmac_f32 %6, " S ", v22\nv_fmac_f32 %7, " S ", v22" \
+    : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7) :: "v20", "v21", "v22");
+template <int MODE>
+__global__ __launch_bounds__(256) void bench_tap(uint32_t *out, int iters, float seed) {
+    const uint32_t byte = (MODE & 2) ? 1u + (threadIdx.x * 37u) % 255u : 77u;
+    const uint32_t sample = (MODE & 4) ? byte : __float_as_uint((float)byte);
+    const float weight = (MODE & 4) ? seed * 0x1p126f : seed * 0x1p-23f;
+    uint32_t r0 = __float_as_uint((float)(threadIdx.x + 1) * 0x1p-22f), r1 = r0 + 3, r2 = r0 + 5, r3 = r0 + 7, r4 = r0 + 11, r5 = r0 + 13, r6 = r0 + 17, r7 = r0 + 19;
+    asm volatile("v_mov_b32 v20, %0\nv_mov_b32 v21, %0\nv_mov_b32 v22, %1" :: "v"(sample), "v"(weight) : "v20", "v21", "v22");
+    for (int it = 0; it < iters; it++) {
+        if (MODE & 1) { REP16(T8("v20")) } else { REP16(T8("v21")) }
+    }
+    if ((r0 ^ r1 ^ r2 ^ r3 ^ r4 ^ r5 ^ r6 ^ r7) == 0x12345678u) out[0] = 1;
+}
+template <int MODE>
+void run_tap(const char *name, uint32_t *d_out, int waves_per_simd) {
+    const int iters = 100;
+    dim3 block(256), grid(256 * waves_per_simd);
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    hipLaunchKernelGGL(bench_tap<MODE>, grid, block, 0, 0, d_out, iters, 1.5f);
+    hipDeviceSynchronize();
+    float best = 1e30f;
+    for (int rep = 0; rep < 3; rep++) {
+        hipEventRecord(e0);
+        hipLaunchKernelGGL(bench_tap<MODE>, grid, block, 0, 0, d_out, iters, 1.5f);
+        hipEventRecord(e1); hipEventSynchronize(e1);
+        float ms; hipEventElapsedTime(&ms, e0, e1);
+        best = ms < best ? ms : best;
+    }
+    printf("%-44s waves/SIMD=%d  %.3f ns per wave-instruction per SIMD\n", name, waves_per_simd, best * 1e6 / (iters * 128.0 * waves_per_simd));
+    fflush(stdout);
 }
 
 template <int OP>
@@ -169,6 +222,28 @@ int main(int argc, char **argv) {
         for (int w : {1, 2, 4, 8}) run<54>("pack: 3 med3 + 2 perm (5 per pixel)", d_out, w, 10);
         for (int w : {1, 2, 4, 8}) run<55>("pack: 2 perm + 2 sat_pk + lshl_or (5)", d_out, w, 10);
         for (int w : {1, 2, 4, 8}) run<56>("pack: 2 ashr_pk + perm (3)", d_out, w, 6);
+        return 0;
+    }
+    if (argc > 1 && argv[1][0] == 'd') {      // taps with a binary32 DENORMAL sample operand against the same instruction on normal operands and against
+                                              // v_fma_mix_f32, at the occupancies of the stream kernels (profiles/f32_denormal_taps_notes.md); twice: the spread
+        for (int round = 0; round < 2; round++) {
+            for (int w : {5, 6}) run<0>("v_fma_f32", d_out, w);
+            for (int w : {5, 6}) run<60>("v_fma_f32 tap, normal", d_out, w);
+            for (int w : {5, 6}) run<61>("v_fma_f32 tap, denormal", d_out, w);
+            for (int w : {5, 6}) run<62>("v_fmac_f32 tap, normal", d_out, w);
+            for (int w : {5, 6}) run<63>("v_fmac_f32 tap, denormal", d_out, w);
+            for (int w : {5, 6}) run<4>("v_fma_mix_f32 lo", d_out, w);
+        }
+        for (int round = 0; round < 2; round++) {
+            for (int w : {5, 6}) run<29>("v_fmac_f32", d_out, w);
+            for (int w : {5, 6}) run_tap<0>("v_fmac_f32 d, v21, v22  one value", d_out, w);
+            for (int w : {5, 6}) run_tap<1>("v_fmac_f32 d, v20, v22  one value", d_out, w);
+            for (int w : {5, 6}) run_tap<2>("v_fmac_f32 d, v21, v22  a byte per lane", d_out, w);
+            for (int w : {5, 6}) run_tap<3>("v_fmac_f32 d, v20, v22  a byte per lane", d_out, w);
+            for (int w : {5, 6}) run_tap<4>("v_fmac_f32 d, v21, v22  one denormal", d_out, w);
+            for (int w : {5, 6}) run_tap<6>("v_fmac_f32 d, v21, v22  a denormal per lane", d_out, w);
+            for (int w : {5, 6}) run_tap<7>("v_fmac_f32 d, v20, v22  a denormal per lane", d_out, w);
+        }
         return 0;
     }
     if (argc > 1) {      // second part only (the first call of the round ran out of its time limit behind v_lshl_add_u32)
