@@ -72,7 +72,8 @@ int chv_debug_set_switch(const char *name, const char *value);
  * "geom_store_batch_hits", "geom_store_builds", "geom_store_bytes", "geom_store_tables"; and "stream_opaque_launches", the launches of
  * tick_bgra_stream that took the opaque-bottom kernels, and "stream_carry_launches", those of them that took the chroma-carry kernels, "stream_f32tap_launches", those of these that took the f32-tap kernels,
  * (process-wide); and "lanczos_ladder_launches", the device launches made by chv_scale_lanczos_to_yuv_ladder (process-wide: one per chunk for a
- * ladder whose rungs all take one route, two for one with rungs on both).  Unknown name -> CHV_ERR_INVALID_VALUE. */
+ * ladder whose rungs all take one route, two for one with rungs on both), and "lanczos_planar_ladder_launches", the same count for
+ * chv_scale_lanczos_ladder (process-wide).  Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
 /* ---- kernels: `enum ComputeKernel`, compute.swift:49-74 ------------------ */
@@ -465,6 +466,27 @@ int chv_scale_lanczos_to_yuv_batch(chv_context *ctx, const chv_image *dsts, cons
 #define CHV_LADDER_PLANE_BYTES 24
 #define CHV_LADDER_CHUNK(n_rungs, planes) (CHV_LADDER_SLOT_BYTES / (((n_rungs) * (planes) + 1) * CHV_LADDER_PLANE_BYTES))
 int chv_scale_lanczos_to_yuv_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, const chv_kernel_opts *opts);
+/* The LADDER of the two 4:2:0 families of chv_scale_lanczos: n_rungs renditions of each of n NV12 or y420p sources as
+ * pictures of the SAME format, all of them in one launch per route.  dsts[r * n + i] is rung r of source i; the call writes the bytes of
+ * n_rungs x n calls of chv_scale_lanczos(ctx, &dsts[r * n + i], &srcs[i]): every plane resampled plane-wise with the tables of its own width and
+ * height, no colour arithmetic.  One list, one shape: all sources have one size and one format, all targets that format, all targets of a rung
+ * one size; rungs may have any sizes (reductions, 1:1, enlargements, the size of another rung).
+ * Errors (all or nothing: every rung of every picture is validated and every rung's route is computed before the first launch; a refused
+ * ladder launches nothing and writes nothing):
+ *   - dsts[0] is not CHV_FMT_NV12 with 2 planes (1 and 2 components) or CHV_FMT_Y420P with 3 planes (1 component each) — this entry has no
+ *     4-component family, a BGRA or RGBA dsts[0] is refused here — or a target plane fails a plane check         -> CHV_ERR_BAD_TARGET;
+ *   - targets that differ in format, sources that differ in format or size, a rung whose targets differ in size, n_rungs < 0, n_rungs >
+ *     CHV_LADDER_MAX_RUNGS, n < 0, a NULL list with non-zero counts                                               -> CHV_ERR_INVALID_VALUE;
+ *   - sources that are consistently not the targets' format or plane structure, a source plane that fails a plane check -> CHV_ERR_BAD_INPUT;
+ *   - a rung for which the 160 KB rule of chv_scale_lanczos refuses any plane                                     -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation                                                           -> CHV_ERR_NOT_IMPLEMENTED.
+ * n_rungs == 0 or n == 0 is a no-op.  Stream order, upload dependencies and a pass's held work as chv_scale_lanczos_batch.
+ * Launches: the rungs that take the wave-per-strip route leave in one launch, the rungs that take the tile route in at most one more, per chunk
+ * (a rung's route is the one its single call takes).  A chunk is what fits one descriptor slot, a picture being its n_rungs x planes target
+ * planes and its `planes` source planes (stored once): CHV_PLANAR_LADDER_CHUNK(n_rungs, planes) pictures, planes = 2 for NV12 and 3 for
+ * y420p.  A longer list is split along the PICTURES: all rungs of a picture leave in one chunk. */
+#define CHV_PLANAR_LADDER_CHUNK(n_rungs, planes) (CHV_LADDER_SLOT_BYTES / ((((n_rungs) + 1) * (planes)) * CHV_LADDER_PLANE_BYTES))
+int chv_scale_lanczos_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

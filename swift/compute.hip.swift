@@ -597,4 +597,28 @@ func scaleLanczosToYuv(_ context: ComputeContext, srcs: [PictureSample], rungs: 
     try check(chv_scale_lanczos_to_yuv_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count), &opts))
     return context
 }
+
+/// A 4:2:0 encoder ladder (chv_scale_lanczos_ladder, DESIGN.md section 4.4.4): rungs[r][i] receives what scaleLanczos(context, src: srcs[i],
+/// target: rungs[r][i]) would write for nv12 or y420p pictures — every rung of every source in one launch per route.  Up to
+/// CHV_LADDER_MAX_RUNGS rungs, each with one target per source; one size per rung, one source size, one format.
+func scaleLanczos(_ context: ComputeContext, srcs: [PictureSample], rungs: [[PictureSample]]) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for src in srcs {
+        guard let image = src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        sources.append(desc)
+    }
+    for rung in rungs {
+        guard rung.count == srcs.count else { throw ComputeError.invalidValue }
+        for target in rung {
+            guard let targetImage = target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            targets.append(targetDesc)
+        }
+    }
+    try check(chv_scale_lanczos_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
+    return context
+}
 #endif

@@ -29,6 +29,7 @@
 #include "lanczos_planar.h"
 #include "lanczos_to_yuv.h"
 #include "lanczos_ladder.h"
+#include "lanczos_planar_ladder.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -124,6 +125,9 @@ void chv::register_lanczos_to_yuv_launcher(LanczosToYuvLauncher fn) { g_lanczos_
 // and for chv_scale_lanczos_to_yuv_ladder (lanczos_ladder.h, kernels_lanczos_ladder.hip.cpp)
 static std::atomic<LanczosLadderLauncher> g_lanczos_ladder_launcher{nullptr};
 void chv::register_lanczos_ladder_launcher(LanczosLadderLauncher fn) { g_lanczos_ladder_launcher.store(fn, std::memory_order_release); }
+// and for chv_scale_lanczos_ladder (lanczos_planar_ladder.h, kernels_lanczos_planar_ladder.hip.cpp)
+static std::atomic<LanczosPlanarLadderLauncher> g_lanczos_planar_ladder_launcher{nullptr};
+void chv::register_lanczos_planar_ladder_launcher(LanczosPlanarLadderLauncher fn) { g_lanczos_planar_ladder_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -145,6 +149,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "stream_opaque_launches")) { *value = debug_counters().stream_opaque_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_carry_launches")) { *value = debug_counters().stream_carry_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_f32tap_launches")) { *value = debug_counters().stream_f32tap_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;
@@ -2609,6 +2614,103 @@ extern "C" int chv_scale_lanczos_to_yuv_ladder(chv_context *c, const chv_image *
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
         if (e != hipSuccess) return hip_fail(e, "lanczos ladder launch");
+    }
+    return CHV_OK;
+}
+
+// ---- chv_scale_lanczos_ladder: every rung of a 4:2:0 ladder in one launch per route ----
+// Pictures per descriptor slot of a chunk: a picture's target planes of every rung and its source planes — stored once — must fit one slot
+// together.  include/chipvideo.h states the rule as CHV_PLANAR_LADDER_CHUNK.
+static_assert(CHV_LADDER_MAX_RUNGS == kLanczosPlanarLadderMaxRungs, "lanczos_planar_ladder.h carries as many rungs as the ABI admits");
+static constexpr int lanczos_planar_ladder_chunk(int n_rungs, int np) { return (int)(kDescSlotBytes / ((size_t)(n_rungs + 1) * np * sizeof(DPlane))); }
+static_assert(lanczos_planar_ladder_chunk(1, 2) == kLanczosChunkNV12 && lanczos_planar_ladder_chunk(1, 3) == kLanczosChunkY420P,
+              "a ladder of one rung is chunked like chv_scale_lanczos_batch");
+static_assert(lanczos_planar_ladder_chunk(CHV_LADDER_MAX_RUNGS, 3) >= 1 && lanczos_planar_ladder_chunk(2, 2) == CHV_PLANAR_LADDER_CHUNK(2, 2) &&
+              lanczos_planar_ladder_chunk(3, 3) == CHV_PLANAR_LADDER_CHUNK(3, 3) && lanczos_planar_ladder_chunk(8, 3) == CHV_PLANAR_LADDER_CHUNK(8, 3),
+              "the longest ladder of the widest format fits one descriptor slot; a chunk is what fits one (include/chipvideo.h states the rule)");
+
+extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
+    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
+    if (n_rungs == 0 || n == 0) return CHV_OK;
+    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    const LanczosPlanarLadderLauncher launcher = g_lanczos_planar_ladder_launcher.load(std::memory_order_acquire);
+    const int np = lanczos_planar_planes(&dsts[0]);
+    if (!np) return fail(CHV_ERR_BAD_TARGET, "Lanczos ladder: target 0 must be nv12 with 2 planes or y420p with 3 (there is no 4-component ladder)");
+    // (one format per list: the list's mistake, not the image's — before anything else is looked at)
+    for (int k = 1; k < n_rungs * n; k++)
+        if (dsts[k].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
+    for (int i = 1; i < n; i++)
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    // a picture's record: the np target planes of rung 0, of rung 1, ..., then the np source planes
+    const size_t per = (size_t)(n_rungs + 1) * np, src_at = (size_t)n_rungs * np;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        for (int r = 0; r < n_rungs; r++) {
+            DPlane pairs[2 * kLanczosPlanarMaxPlanes];
+            int rc = lanczos_planar_pairs(c, &dsts[(size_t)r * n + i], &srcs[i], np, r * n + i, pairs);
+            if (rc) return rc;
+            for (int p = 0; p < np; p++) {
+                pi[r * np + p] = pairs[2 * p];
+                pi[src_at + p] = pairs[2 * p + 1];
+                const DPlane &d0 = planes[r * np + p];
+                if (pairs[2 * p].w != d0.w || pairs[2 * p].h != d0.h)
+                    return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p, pairs[2 * p].w,
+                                pairs[2 * p].h, d0.w, d0.h);
+            }
+        }
+        for (int p = 0; p < np; p++)
+            if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
+                return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
+                            pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos ladder kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    // two tables per plane per rung, from the shared cache (planes of one geometry share theirs); every reference is held until the last
+    // launch is enqueued, so a ladder that brings more geometries than the cache has room for cannot lose a table it has already collected
+    LanczosRef refs[2 * kLanczosPlanarMaxPlanes * CHV_LADDER_MAX_RUNGS];
+    LanczosPlanarLadderJob job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs; job.n_planes = np;
+    for (int p = 0; p < np; p++) { job.src_w[p] = planes[src_at + p].w; job.src_h[p] = planes[src_at + p].h; }
+    for (int r = 0; r < n_rungs; r++) {
+        for (int p = 0; p < np; p++) {
+            const DPlane &d = planes[r * np + p];
+            LanczosRef &rx = refs[2 * (r * kLanczosPlanarMaxPlanes + p)], &ry = refs[2 * (r * kLanczosPlanarMaxPlanes + p) + 1];
+            rc = lanczos_table(c, job.src_w[p], d.w, &rx);
+            if (rc) return rc;
+            rc = lanczos_table(c, job.src_h[p], d.h, &ry);
+            if (rc) return rc;
+            job.rung[r].tab[p] = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
+            job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
+        }
+    }
+    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES, so
+    // all rungs of a picture leave in one chunk
+    const int per_slot = lanczos_planar_ladder_chunk(n_rungs, np);
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_planar_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        if (e != hipSuccess) return hip_fail(e, "lanczos planar ladder launch");
     }
     return CHV_OK;
 }

@@ -51,6 +51,7 @@ struct DebugCounters {
     std::atomic<unsigned long long> stream_carry_launches{0};        // ... of which: the chroma-carry kernels (kernels_stream_carry.hip.cpp)
     std::atomic<unsigned long long> stream_f32tap_launches{0};       // ... of which: the f32-tap kernels (kernels_stream_dn.hip.cpp)
     std::atomic<unsigned long long> lanczos_ladder_launches{0};      // device launches made by chv_scale_lanczos_to_yuv_ladder
+    std::atomic<unsigned long long> lanczos_planar_ladder_launches{0};      // device launches made by chv_scale_lanczos_ladder
 };
 DebugCounters &debug_counters();
 

@@ -553,6 +553,23 @@ inline ComputeContext scaleLanczosToYuv(ComputeContext ctx, const std::vector<st
     return ctx;
 }
 
+// A 4:2:0 encoder ladder (chv_scale_lanczos_ladder): rungs[r][i] receives what scaleLanczos(ctx, rungs[r][i], srcs[i])
+// would write for nv12 or y420p pictures — every rung of every source in one launch per route (the wave-per-strip rungs in one, the tile rungs
+// in at most one more).  Up to CHV_LADDER_MAX_RUNGS rungs, each with one target per source; one size per rung, one source size, one format.
+inline ComputeContext scaleLanczos(ComputeContext ctx, const std::vector<std::vector<PictureSample>> &rungs, const std::vector<PictureSample> &srcs) {
+    const size_t n = srcs.size();
+    std::vector<chv_image> d(rungs.size() * n), s(n);
+    for (size_t i = 0; i < n; i++)
+        if (!describe(srcs[i], &s[i])) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    for (size_t r = 0; r < rungs.size(); r++) {
+        if (rungs[r].size() != n) throw ComputeError(CHV_ERR_INVALID_VALUE, "a rung has one target per source");
+        for (size_t i = 0; i < n; i++)
+            if (!describe(rungs[r][i], &d[r * n + i])) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    }
+    check(chv_scale_lanczos_ladder(ctx.get(), d.data(), (int)rungs.size(), s.data(), (int)n));
+    return ctx;
+}
+
 // Many independent ticks as ONE launch (chv_batch_*): what a host with several mixers / streams on a device
 // (composer.swift:203-224) uses instead of one chv_composite per tick; byte-identical to running them one by one.
 struct Tick { PictureSample target; bool clearFirst = true; std::vector<TickLayer> layers; };
