@@ -73,7 +73,9 @@ int chv_debug_set_switch(const char *name, const char *value);
  * tick_bgra_stream that took the opaque-bottom kernels, and "stream_carry_launches", those of them that took the chroma-carry kernels, "stream_f32tap_launches", those of these that took the f32-tap kernels,
  * (process-wide); and "lanczos_ladder_launches", the device launches made by chv_scale_lanczos_to_yuv_ladder (process-wide: one per chunk for a
  * ladder whose rungs all take one route, two for one with rungs on both), and "lanczos_planar_ladder_launches", the same count for
- * chv_scale_lanczos_ladder (process-wide).  Unknown name -> CHV_ERR_INVALID_VALUE. */
+ * chv_scale_lanczos_ladder (process-wide), and "lanczos_420_ladder_launches", the same count for the cross-format path (NV12 -> y420p,
+ * y420p -> NV12) of chv_scale_lanczos_420 and chv_scale_lanczos_420_ladder (process-wide; same-format pairs through those entries are forwarded
+ * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to).  Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
 /* ---- kernels: `enum ComputeKernel`, compute.swift:49-74 ------------------ */
@@ -487,6 +489,33 @@ int chv_scale_lanczos_to_yuv_ladder(chv_context *ctx, const chv_image *dsts, int
  * y420p.  A longer list is split along the PICTURES: all rungs of a picture leave in one chunk. */
 #define CHV_PLANAR_LADDER_CHUNK(n_rungs, planes) (CHV_LADDER_SLOT_BYTES / ((((n_rungs) + 1) * (planes)) * CHV_LADDER_PLANE_BYTES))
 int chv_scale_lanczos_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
+/* Lanczos-3 BETWEEN the two 4:2:0 packings: any of the four (source packing, target packing) pairs of NV12 and
+ * y420p.  A 4:2:0 picture of either packing has three LOGICAL 1-component images Y, Cb and Cr — NV12: Cb and Cr are components 0 and 1 of plane
+ * 1, y420p: planes 1 and 2; chroma images are max(1, w / 2) x max(1, h / 2) as everywhere else.  Each logical plane of src is resampled to the
+ * size of the same logical plane of dst exactly as chv_scale_lanczos resamples a 1-component plane: its own tables per axis from its own width
+ * and height, horizontal then vertical pass, fmaf per tap from 0 with taps ascending, indices clamped to the plane's edge, float intermediate,
+ * convert_uchar_sat_rte.  No colour arithmetic, no re-siting, no cross-plane term: the bytes are those chv_scale_lanczos writes for the
+ * same-format pair of the same sizes, stored in the other packing; at equal sizes the call is an exact repack.  Same-format pairs (NV12 -> NV12,
+ * y420p -> y420p) are accepted and forwarded: they write the bytes of chv_scale_lanczos / chv_scale_lanczos_ladder.
+ * chv_scale_lanczos_420_ladder: dsts[r * n + i] is rung r of source i; the call writes the bytes of n_rungs x n single calls.  All sources have
+ * one size and one format, all targets one format (which may differ from the sources'), all targets of a rung one size; rungs may have any
+ * sizes.  All or nothing; n_rungs == 0 or n == 0 is a no-op.
+ * Errors (nothing launched, nothing written):
+ *   - dst is not CHV_FMT_NV12 with 2 planes (1 and 2 components) or CHV_FMT_Y420P with 3 planes (1 component each), a target plane fails a plane
+ *     check, a y420p target whose planes 1 and 2 differ in width or height                                        -> CHV_ERR_BAD_TARGET;
+ *   - the same conditions on src                                                                                  -> CHV_ERR_BAD_INPUT;
+ *   - targets of a ladder that differ in format, sources that differ in format or size, a rung whose targets differ in size, n_rungs < 0,
+ *     n_rungs > CHV_LADDER_MAX_RUNGS, n < 0, a NULL list with non-zero counts, a rung for which the 160 KB rule of chv_scale_lanczos refuses
+ *     any logical plane                                                                                           -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation                                                           -> CHV_ERR_NOT_IMPLEMENTED.
+ * Stream order, upload dependencies, a pass's held work and table lifetime as chv_scale_lanczos_batch.  The entries read no switch: a rung
+ * takes the wave-per-strip route when no logical plane has more than 22 taps on an axis and the tile route otherwise.
+ * Launches of a cross pair: one per route per chunk, at most two per chunk.  A chunk is what fits one descriptor slot, a picture being its
+ * n_rungs x target planes + source planes records: CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) pictures, planes = 2 for NV12 and 3
+ * for y420p (for same-format lists it equals CHV_PLANAR_LADDER_CHUNK).  A longer list is split along the PICTURES. */
+#define CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) (CHV_LADDER_SLOT_BYTES / (((n_rungs) * (dst_planes) + (src_planes)) * CHV_LADDER_PLANE_BYTES))
+int chv_scale_lanczos_420(chv_context *ctx, const chv_image *dst, const chv_image *src);
+int chv_scale_lanczos_420_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

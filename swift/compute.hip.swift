@@ -621,4 +621,41 @@ func scaleLanczos(_ context: ComputeContext, srcs: [PictureSample], rungs: [[Pic
     try check(chv_scale_lanczos_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
     return context
 }
+
+/// Lanczos-3 between the two 4:2:0 packings (chv_scale_lanczos_420, DESIGN.md section 4.4.5): an nv12 or y420p picture into an nv12 or y420p
+/// picture, any of the four pairs — the logical planes Y, Cb and Cr resampled one by one and stored in the target's packing; at equal sizes
+/// an exact repack.  A same-format pair writes what scaleLanczos writes.
+func scaleLanczos420(_ context: ComputeContext, src: PictureSample, target: PictureSample) throws -> ComputeContext {
+    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 3) else {
+        throw ComputeError.badTarget
+    }
+    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 3) else {
+        throw ComputeError.badInputData(description: "Bad input image")
+    }
+    try check(chv_scale_lanczos_420(context.handle, &targetDesc, &desc))
+    return context
+}
+
+/// The ladder of it (chv_scale_lanczos_420_ladder): rungs[r][i] receives what scaleLanczos420(context, src: srcs[i], target: rungs[r][i])
+/// would write — one format for all sources, one for all targets, which may be the other packing.
+func scaleLanczos420(_ context: ComputeContext, srcs: [PictureSample], rungs: [[PictureSample]]) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for src in srcs {
+        guard let image = src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        sources.append(desc)
+    }
+    for rung in rungs {
+        guard rung.count == srcs.count else { throw ComputeError.invalidValue }
+        for target in rung {
+            guard let targetImage = target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            targets.append(targetDesc)
+        }
+    }
+    try check(chv_scale_lanczos_420_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
+    return context
+}
 #endif

@@ -9,7 +9,8 @@
    on the device — one full-canvas layer through the composite kernels (colour conversion + bilinear
    scale in one launch) or a separable Lanczos-3 resample: without conversion (BGRA -> BGRA, nv12 -> nv12,
    y420p -> y420p; chv_scale_lanczos, a 4:2:0 picture plane by plane), or BGRA / RGBA -> nv12 / y420p through
-   the integer matrix (chv_scale_lanczos_to_yuv).
+   the integer matrix (chv_scale_lanczos_to_yuv), or — only with convert420 — nv12 <-> y420p, the logical planes
+   resampled one by one and stored in the other packing (chv_scale_lanczos_420).
    It replaces filter.pict.swift when GPGPU_HIP is defined.
 */
 #if GPGPU_HIP
@@ -29,6 +30,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                 scaler: PictureScaler = .bilinear,
                 integerMatrix: Bool = true,
                 colorspace: Int32 = 0,
+                convert420: Bool = false,
                 computeContext: ComputeContext? = nil) {
         self.clock = clock
         self.outputSize = outputSize
@@ -36,6 +38,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
         self.scaler = scaler
         self.integerMatrix = integerMatrix
         self.colorspace = colorspace
+        self.convert420 = convert420
         do {
             if let context = computeContext {
                 self.context = createComputeContext(sharing: context)
@@ -65,6 +68,10 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                         if strongSelf.integerMatrix && rgbIn && (format == .nv12 || format == .y420p) {
                             // (the float full-range matrix has no Lanczos form)
                             return try scaleLanczosToYuv($0, src: src, target: dst, colorspace: strongSelf.colorspace)
+                        }
+                        let yuvIn = src.pixelFormat() == .nv12 || src.pixelFormat() == .y420p
+                        if strongSelf.convert420 && yuvIn && (format == .nv12 || format == .y420p) && src.pixelFormat() != format {
+                            return try scaleLanczos420($0, src: src, target: dst)
                         }
                         guard src.pixelFormat() == format, format == .BGRA || format == .nv12 || format == .y420p else {
                             throw ComputeError.notImplemented
@@ -128,6 +135,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
     let scaler: PictureScaler
     let integerMatrix: Bool
     let colorspace: Int32      // chv_colorspace of the integer matrix (the Lanczos conversion)
+    let convert420: Bool       // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
     var context: ComputeContext?
 }
 #endif

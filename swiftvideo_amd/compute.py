@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -845,6 +845,34 @@ def scaleLanczosLadder(ctx, rungs, srcs):
     return LanczosLadder(rungs, srcs).run(ctx)
 
 
+def scaleLanczos420(ctx, dst, src):
+    """Lanczos-3 resize of an nv12 or y420p picture into an nv12 or y420p picture, any of the four pairs (chv_scale_lanczos_420, DESIGN.md
+    section 4.4.5): the logical planes Y, Cb and Cr resampled one by one as scaleLanczos resamples a 1-component plane, stored in the target's
+    packing — no colour arithmetic; at equal sizes an exact repack.  A same-format pair writes what scaleLanczos writes."""
+    d, s = _image_desc(dst), _image_desc(src)
+    if d is None:
+        raise ComputeError(4, "target has no GPU image buffer")
+    if s is None:
+        raise ComputeError(5, "Bad input image")
+    cv.check(cv.load().chv_scale_lanczos_420(ctx.handle, C.byref(d), C.byref(s)))
+    return ctx
+
+
+class Lanczos420Ladder(LanczosLadder):
+    """LanczosLadder whose targets may have the other 4:2:0 packing than its sources (chv_scale_lanczos_420_ladder):
+    one format for all sources, one for all targets; one launch per route for a cross pair, the bytes of the single scaleLanczos420 calls."""
+
+    def run(self, ctx):
+        cv.check(cv.load().chv_scale_lanczos_420_ladder(ctx.handle, self._d, self.n_rungs, self._s, self.n))
+        return ctx
+
+
+def scaleLanczos420Ladder(ctx, rungs, srcs):
+    """Every rung of a 4:2:0 ladder whose targets may have the other packing than its sources (chv_scale_lanczos_420_ladder): rungs[r][i]
+    receives what scaleLanczos420(ctx, rungs[r][i], srcs[i]) would write."""
+    return Lanczos420Ladder(rungs, srcs).run(ctx)
+
+
 # ---- pipeline operators -----------------------------------------------------------------------
 class GPUBarrierUpload:
     """Tx<PictureSample, PictureSample>, compute.swift:175-198: owns a context sharing
@@ -885,18 +913,19 @@ class PictureFilter:
     constructor shape: a context of its own, sharing the given one).  One full-canvas layer through the
     composite kernels: colour conversion + bilinear scale in one launch (`scaler="bilinear"`, any format
     pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p
-    without a conversion, a 4:2:0 picture plane by plane; BGRA or RGBA -> nv12 or y420p through the integer matrix, scaleLanczosToYuv).
+    without a conversion, a 4:2:0 picture plane by plane; BGRA or RGBA -> nv12 or y420p through the integer matrix, scaleLanczosToYuv;
+    with `convert420=True` also nv12 <-> y420p, scaleLanczos420 — off by default: a host that did not ask for a repack gets the error it got).
     CPU samples are uploaded first; the sample's time stamps, ids and transform state are carried over.
     Results land in a ring of `numberBackingImages` device images like the mixer's (mix.video.swift:148-167)."""
 
     numberBackingImages = 10
 
     def __init__(self, outputSize, outputFormat=PixelFormat.BGRA, computeContext=None, scaler="bilinear",
-                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True):
+                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False):
         """integerMatrix: an RGB picture converted to a 4:2:0 format goes through the integer BT.601/709 matrix of `colorspace`
         (img_*_int, DESIGN.md 4.5: what an encoder expects); False selects the reference's own float kernels (img_bgra_nv12 ...,
         full range, kernels.cl.swift:96-99)."""
-        self.integerMatrix = integerMatrix
+        self.integerMatrix, self.convert420 = integerMatrix, convert420
         if scaler not in ("bilinear", "lanczos"):
             raise ComputeError(0, f"unknown scaler {scaler!r}")
         try:
@@ -939,6 +968,8 @@ class PictureFilter:
             if self.scaler == "lanczos" and self.integerMatrix and src.pixelFormat() in (PixelFormat.BGRA, PixelFormat.RGBA) \
                     and self.outputFormat in (PixelFormat.nv12, PixelFormat.y420p):
                 scaleLanczosToYuv(ctx, dst, src, self.colorspace)       # (the float full-range matrix has no Lanczos form)
+            elif self.scaler == "lanczos" and self.convert420 and {src.pixelFormat(), self.outputFormat} == {PixelFormat.nv12, PixelFormat.y420p}:
+                scaleLanczos420(ctx, dst, src)
             elif self.scaler == "lanczos":
                 if src.pixelFormat() != self.outputFormat or self.outputFormat not in (PixelFormat.BGRA, PixelFormat.nv12, PixelFormat.y420p):
                     raise ComputeError(9, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only")

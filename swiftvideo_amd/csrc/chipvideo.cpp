@@ -30,6 +30,7 @@
 #include "lanczos_to_yuv.h"
 #include "lanczos_ladder.h"
 #include "lanczos_planar_ladder.h"
+#include "lanczos_420.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -128,6 +129,9 @@ void chv::register_lanczos_ladder_launcher(LanczosLadderLauncher fn) { g_lanczos
 // and for chv_scale_lanczos_ladder (lanczos_planar_ladder.h, kernels_lanczos_planar_ladder.hip.cpp)
 static std::atomic<LanczosPlanarLadderLauncher> g_lanczos_planar_ladder_launcher{nullptr};
 void chv::register_lanczos_planar_ladder_launcher(LanczosPlanarLadderLauncher fn) { g_lanczos_planar_ladder_launcher.store(fn, std::memory_order_release); }
+// and for the cross pairs of chv_scale_lanczos_420 / chv_scale_lanczos_420_ladder (lanczos_420.h, kernels_lanczos_420.hip.cpp)
+static std::atomic<Lanczos420Launcher> g_lanczos_420_launcher{nullptr};
+void chv::register_lanczos_420_launcher(Lanczos420Launcher fn) { g_lanczos_420_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -150,6 +154,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "stream_carry_launches")) { *value = debug_counters().stream_carry_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_f32tap_launches")) { *value = debug_counters().stream_f32tap_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;
@@ -2713,6 +2718,128 @@ extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, i
         if (e != hipSuccess) return hip_fail(e, "lanczos planar ladder launch");
     }
     return CHV_OK;
+}
+
+// ---- chv_scale_lanczos_420 / chv_scale_lanczos_420_ladder: Lanczos-3 between NV12 and y420p ----
+static constexpr int lanczos_420_chunk(int n_rungs, int dnp, int snp) { return (int)(kDescSlotBytes / (((size_t)n_rungs * dnp + snp) * sizeof(DPlane))); }
+static_assert(lanczos_420_chunk(3, 2, 3) == CHV_420_LADDER_CHUNK(3, 2, 3) && lanczos_420_chunk(8, 3, 2) == CHV_420_LADDER_CHUNK(8, 3, 2) &&
+              lanczos_420_chunk(8, 3, 2) >= 1 && lanczos_420_chunk(4, 3, 3) == lanczos_planar_ladder_chunk(4, 3) &&
+              CHV_420_LADDER_CHUNK(5, 2, 2) == CHV_PLANAR_LADDER_CHUNK(5, 2),
+              "a chunk is what fits one descriptor slot (include/chipvideo.h states the rule); same-format lists are chunked like chv_scale_lanczos_ladder");
+
+// every plane of one 4:2:0 picture of either packing -> out[0 .. np); *np 0 and `err` for anything else.  A y420p picture's chroma planes
+// must have one size: they are two images of one logical grid.
+static int lanczos_420_planes(chv_context *c, const chv_image *img, int err, const char *what, int idx, DPlane *out, int *np) {
+    *np = lanczos_planar_planes(img);
+    if (!*np) return fail(err, "Lanczos 4:2:0 %s %d must be nv12 with 2 planes or y420p with 3", what, idx);
+    for (int p = 0; p < *np; p++) {
+        int rc = plane_to_device(img->planes[p], lanczos_planar_comps(img->format, p), c->device, &out[p], err, what, p);
+        if (rc) return rc;
+    }
+    if (*np == 3 && (out[1].w != out[2].w || out[1].h != out[2].h))
+        return fail(err, "Lanczos 4:2:0 %s %d: chroma planes of %dx%d and %dx%d (a y420p picture's planes 1 and 2 have one size)", what, idx, out[1].w, out[1].h,
+                    out[2].w, out[2].h);
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
+    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
+    if (n_rungs == 0 || n == 0) return CHV_OK;
+    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    const Lanczos420Launcher launcher = g_lanczos_420_launcher.load(std::memory_order_acquire);
+    const int dnp = lanczos_planar_planes(&dsts[0]), snp = lanczos_planar_planes(&srcs[0]);
+    if (!dnp) return fail(CHV_ERR_BAD_TARGET, "Lanczos 4:2:0: target 0 must be nv12 with 2 planes or y420p with 3");
+    if (!snp) return fail(CHV_ERR_BAD_INPUT, "Lanczos 4:2:0: source 0 must be nv12 with 2 planes or y420p with 3");
+    // (one format per list: the list's mistake, not the image's — before anything else is looked at)
+    for (int k = 1; k < n_rungs * n; k++)
+        if (dsts[k].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
+    for (int i = 1; i < n; i++)
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    // a picture's record: the dnp target planes of rung 0, of rung 1, ..., then the snp source planes
+    const size_t per = (size_t)n_rungs * dnp + snp, src_at = (size_t)n_rungs * dnp;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        for (int r = 0; r < n_rungs; r++) {
+            int np = 0;
+            int rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
+            if (rc) return rc;
+            for (int p = 0; p < dnp; p++)
+                if (pi[r * dnp + p].w != planes[r * dnp + p].w || pi[r * dnp + p].h != planes[r * dnp + p].h)
+                    return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p,
+                                pi[r * dnp + p].w, pi[r * dnp + p].h, planes[r * dnp + p].w, planes[r * dnp + p].h);
+        }
+        int np = 0;
+        int rc = lanczos_420_planes(c, &srcs[i], CHV_ERR_BAD_INPUT, "input", i, pi + src_at, &np);
+        if (rc) return rc;
+        for (int p = 0; p < snp; p++)
+            if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
+                return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
+                            pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
+    }
+    // same-format lists are chv_scale_lanczos_ladder's: its launchers, its counter, its bytes
+    if (dnp == snp) return chv_scale_lanczos_ladder(c, dsts, n_rungs, srcs, n);
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no 4:2:0 conversion Lanczos kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    // two tables per logical plane per rung, from the shared cache; every reference is held until the last launch is enqueued
+    LanczosRef refs[2 * kLanczosPlanarMaxPlanes * CHV_LADDER_MAX_RUNGS];
+    Lanczos420Job job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs; job.dst_planes = dnp; job.src_planes = snp;
+    job.luma_w = planes[src_at].w; job.luma_h = planes[src_at].h;
+    job.chroma_w = planes[src_at + 1].w; job.chroma_h = planes[src_at + 1].h;
+    for (int r = 0; r < n_rungs; r++) {
+        for (int p = 0; p < dnp; p++) {
+            const DPlane &d = planes[r * dnp + p];
+            LanczosRef &rx = refs[2 * (r * kLanczosPlanarMaxPlanes + p)], &ry = refs[2 * (r * kLanczosPlanarMaxPlanes + p) + 1];
+            rc = lanczos_table(c, p ? job.chroma_w : job.luma_w, d.w, &rx);
+            if (rc) return rc;
+            rc = lanczos_table(c, p ? job.chroma_h : job.luma_h, d.h, &ry);
+            if (rc) return rc;
+            job.rung[r].tab[p] = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
+            job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
+        }
+    }
+    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES
+    const int per_slot = lanczos_420_chunk(n_rungs, dnp, snp);
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_420_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        if (e != hipSuccess) return hip_fail(e, "lanczos 4:2:0 ladder launch");
+    }
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_420(chv_context *c, const chv_image *dst, const chv_image *src) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    DPlane pl[kLanczosPlanarMaxPlanes];
+    int dnp = 0, snp = 0;
+    int rc = lanczos_420_planes(c, dst, CHV_ERR_BAD_TARGET, "target", 0, pl, &dnp);
+    if (rc) return rc;
+    rc = lanczos_420_planes(c, src, CHV_ERR_BAD_INPUT, "input", 0, pl, &snp);
+    if (rc) return rc;
+    // a same-format pair is chv_scale_lanczos's; a cross pair is the ladder of one rung and one picture
+    return dnp == snp ? chv_scale_lanczos(c, dst, src) : chv_scale_lanczos_420_ladder(c, dst, 1, src, 1);
 }
 
 // ---------------------------------------------------------------------------

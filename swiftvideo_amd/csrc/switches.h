@@ -52,6 +52,7 @@ struct DebugCounters {
     std::atomic<unsigned long long> stream_f32tap_launches{0};       // ... of which: the f32-tap kernels (kernels_stream_dn.hip.cpp)
     std::atomic<unsigned long long> lanczos_ladder_launches{0};      // device launches made by chv_scale_lanczos_to_yuv_ladder
     std::atomic<unsigned long long> lanczos_planar_ladder_launches{0};      // device launches made by chv_scale_lanczos_ladder
+    std::atomic<unsigned long long> lanczos_420_ladder_launches{0};         // device launches made by the cross-format path of chv_scale_lanczos_420 / _420_ladder
 };
 DebugCounters &debug_counters();
 

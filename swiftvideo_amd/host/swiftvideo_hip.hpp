@@ -570,6 +570,33 @@ inline ComputeContext scaleLanczos(ComputeContext ctx, const std::vector<std::ve
     return ctx;
 }
 
+// Lanczos-3 between the two 4:2:0 packings (chv_scale_lanczos_420): an nv12 or y420p picture into an nv12 or y420p
+// picture, any of the four pairs — the logical planes Y, Cb and Cr resampled one by one as scaleLanczos resamples a 1-component plane and
+// stored in the target's packing; at equal sizes an exact repack.  A same-format pair writes what scaleLanczos writes.
+inline ComputeContext scaleLanczos420(ComputeContext ctx, const PictureSample &dst, const PictureSample &src) {
+    chv_image d, s;
+    if (!describe(dst, &d)) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    if (!describe(src, &s)) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    check(chv_scale_lanczos_420(ctx.get(), &d, &s));
+    return ctx;
+}
+
+// The ladder of it (chv_scale_lanczos_420_ladder): rungs[r][i] receives what scaleLanczos420(ctx, rungs[r][i], srcs[i]) would write — one format
+// for all sources, one for all targets, which may be the other packing; a cross pair leaves in one launch per route.
+inline ComputeContext scaleLanczos420(ComputeContext ctx, const std::vector<std::vector<PictureSample>> &rungs, const std::vector<PictureSample> &srcs) {
+    const size_t n = srcs.size();
+    std::vector<chv_image> d(rungs.size() * n), s(n);
+    for (size_t i = 0; i < n; i++)
+        if (!describe(srcs[i], &s[i])) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    for (size_t r = 0; r < rungs.size(); r++) {
+        if (rungs[r].size() != n) throw ComputeError(CHV_ERR_INVALID_VALUE, "a rung has one target per source");
+        for (size_t i = 0; i < n; i++)
+            if (!describe(rungs[r][i], &d[r * n + i])) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    }
+    check(chv_scale_lanczos_420_ladder(ctx.get(), d.data(), (int)rungs.size(), s.data(), (int)n));
+    return ctx;
+}
+
 // Many independent ticks as ONE launch (chv_batch_*): what a host with several mixers / streams on a device
 // (composer.swift:203-224) uses instead of one chv_composite per tick; byte-identical to running them one by one.
 struct Tick { PictureSample target; bool clearFirst = true; std::vector<TickLayer> layers; };
@@ -844,7 +871,7 @@ private:
 //      (filter.pict.swift:20-47).  Converts a picture to outputFormat at outputSize on the device: one
 //      full-canvas layer through the composite kernels (colour conversion + bilinear scale in one launch),
 //      or a separable Lanczos-3 resample (BGRA -> BGRA, nv12 -> nv12, y420p -> y420p without a conversion; BGRA or RGBA -> nv12 or y420p through
-//      the integer matrix, scaleLanczosToYuv).  CPU samples are uploaded first; results land in a
+//      the integer matrix, scaleLanczosToYuv; with convert420 set also nv12 <-> y420p, scaleLanczos420).  CPU samples are uploaded first; results land in a
 //      ring of device images like the mixer's (mix.video.swift:148-167). ------------------------------------
 class PictureFilter {
 public:
@@ -864,6 +891,7 @@ public:
         return defaultComputeKernelFromString(name);
     }
     bool integerMatrix = true;
+    bool convert420 = false;          // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
 
     EventBox<PictureSample> operator()(const PictureSample &sample) {
         EventBox<PictureSample> r;
@@ -874,6 +902,10 @@ public:
             if (scaler_ == Scaler::lanczos && integerMatrix && rgb && (format_ == PixelFormat::nv12 || format_ == PixelFormat::y420p)) {
                 // (the float full-range matrix has no Lanczos form)
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczosToYuv(c, dst, src, colorspace_); });
+            } else if (scaler_ == Scaler::lanczos && convert420 && src.pixelFormat() != format_ &&
+                       (src.pixelFormat() == PixelFormat::nv12 || src.pixelFormat() == PixelFormat::y420p) &&
+                       (format_ == PixelFormat::nv12 || format_ == PixelFormat::y420p)) {
+                usingContext(context_, [&](ComputeContext c) { return scaleLanczos420(c, dst, src); });
             } else if (scaler_ == Scaler::lanczos) {
                 if (src.pixelFormat() != format_ || (format_ != PixelFormat::BGRA && format_ != PixelFormat::nv12 && format_ != PixelFormat::y420p))
                     throw ComputeError(CHV_ERR_NOT_IMPLEMENTED, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only");
