@@ -75,7 +75,9 @@ int chv_debug_set_switch(const char *name, const char *value);
  * ladder whose rungs all take one route, two for one with rungs on both), and "lanczos_planar_ladder_launches", the same count for
  * chv_scale_lanczos_ladder (process-wide), and "lanczos_420_ladder_launches", the same count for the cross-format path (NV12 -> y420p,
  * y420p -> NV12) of chv_scale_lanczos_420 and chv_scale_lanczos_420_ladder (process-wide; same-format pairs through those entries are forwarded
- * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to).  Unknown name -> CHV_ERR_INVALID_VALUE. */
+ * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to), and "lanczos_from_yuv_launches", the device
+ * launches made by chv_scale_lanczos_from_yuv and chv_scale_lanczos_from_yuv_batch (process-wide: one per call, one per chunk).
+ * Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
 /* ---- kernels: `enum ComputeKernel`, compute.swift:49-74 ------------------ */
@@ -516,6 +518,28 @@ int chv_scale_lanczos_ladder(chv_context *ctx, const chv_image *dsts, int n_rung
 #define CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) (CHV_LADDER_SLOT_BYTES / (((n_rungs) * (dst_planes) + (src_planes)) * CHV_LADDER_PLANE_BYTES))
 int chv_scale_lanczos_420(chv_context *ctx, const chv_image *dst, const chv_image *src);
 int chv_scale_lanczos_420_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
+/* Lanczos-3 resize of one NV12 or y420p picture INTO a BGRA or RGBA plane of `dst`'s size, in one launch: the decoder side's rendition
+ * (DESIGN.md section 4.4.6).  The logical planes Y, Cb and Cr of `src` (NV12: Cb and Cr are components 0 and 1 of plane 1; y420p: planes 1
+ * and 2) are each resampled to dst's w x h exactly as chv_scale_lanczos resamples a 1-component plane — the chroma planes straight from
+ * max(1, w / 2) x max(1, h / 2) of the source's w x h, every plane with its own tables per axis from its own width and height, horizontal then
+ * vertical pass, fmaf per tap from 0 with taps ascending, indices clamped to the plane's edge, float intermediate, convert_uchar_sat_rte; no
+ * re-siting, no cross-plane term.  The three CODES of a pixel go through the integer matrix of section 4.2 for `opts->colorspace & 3`
+ * (opts == NULL: BT.601 limited); the pixel is stored as B, G, R, 255 (CHV_FMT_BGRA) or R, G, B, 255 (CHV_FMT_RGBA).  Nothing is blended with
+ * what `dst` held.  Stream order, upload dependencies, a pass's held work and table lifetime are those of chv_scale_lanczos_batch.
+ * Errors (nothing is launched, nothing is written):
+ *   - `dst` is not one 4-component plane whose format is CHV_FMT_BGRA or CHV_FMT_RGBA, or that plane fails a plane check -> CHV_ERR_BAD_TARGET;
+ *   - `src` is not CHV_FMT_NV12 with 2 planes (1 and 2 components) or CHV_FMT_Y420P with 3 planes (1 component each, planes 1 and 2 of one
+ *     size), a chroma plane is not max(1, w / 2) x max(1, h / 2) of plane 0's w x h, or a source plane fails a plane check -> CHV_ERR_BAD_INPUT;
+ *   - a logical plane whose own (in, out) sizes the 160 KB rule of chv_scale_lanczos refuses                  -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation                                                       -> CHV_ERR_NOT_IMPLEMENTED.
+ * The entries read no switch: a picture takes the wave-per-strip route when no logical plane has more than 22 taps on an axis and the tile
+ * route otherwise.  chv_scale_lanczos and every other entry keep their statuses: NV12 -> BGRA there stays CHV_ERR_BAD_INPUT. */
+int chv_scale_lanczos_from_yuv(chv_context *ctx, const chv_image *dst, const chv_image *src, const chv_kernel_opts *opts);
+/* n such conversions of ONE geometry, ONE source format, ONE target format and the one colourspace of `opts` in one launch per chunk; same bytes
+ * as n calls of chv_scale_lanczos_from_yuv.  Another geometry, source format or target format in the list -> CHV_ERR_INVALID_VALUE, all or
+ * nothing; every other error as above; n == 0 is a no-op.  A chunk is what fits one descriptor slot, counted as chv_scale_lanczos_to_yuv_batch
+ * counts it: 83 pictures from NV12 (3 plane records each) or 62 from y420p (4 plane records each). */
+int chv_scale_lanczos_from_yuv_batch(chv_context *ctx, const chv_image *dsts, const chv_image *srcs, int n, const chv_kernel_opts *opts);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

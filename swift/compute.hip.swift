@@ -571,6 +571,46 @@ func scaleLanczosToYuv(_ context: ComputeContext, pairs: [(src: PictureSample, t
     return context
 }
 
+// MARK: - Lanczos-3 resize of an nv12 or y420p picture into a BGRA / RGBA picture (no reference counterpart; used by filter.pict.hip.swift)
+// One launch (chv_scale_lanczos_from_yuv, DESIGN.md section 4.4.6): Y, Cb and Cr are each resampled to the target's size as scaleLanczos
+// resamples a 1-component plane, rounded to codes, and a pixel's three codes go through the integer BT.601/709 matrix of `colorspace`
+// (chv_colorspace; BT.601 limited by default) — the decoder side's rendition: a preview, a thumbnail, a layer prepared for a BGRA canvas.
+
+func scaleLanczosFromYuv(_ context: ComputeContext, src: PictureSample, target: PictureSample,
+                         colorspace: Int32 = 0) throws -> ComputeContext {
+    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 3) else {
+        throw ComputeError.badTarget
+    }
+    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 3) else {
+        throw ComputeError.badInputData(description: "Bad input image")
+    }
+    var opts = chv_kernel_opts()
+    opts.colorspace = colorspace
+    try check(chv_scale_lanczos_from_yuv(context.handle, &targetDesc, &desc, &opts))
+    return context
+}
+
+/// n such conversions of one geometry, one source format, one target format and one colourspace in one launch per chunk (83 pictures from
+/// nv12, 62 from y420p; chv_scale_lanczos_from_yuv_batch): the previews of several decoded streams per tick
+func scaleLanczosFromYuv(_ context: ComputeContext, pairs: [(src: PictureSample, target: PictureSample)],
+                         colorspace: Int32 = 0) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for pair in pairs {
+        guard let targetImage = pair.target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+            throw ComputeError.badTarget
+        }
+        guard let image = pair.src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        targets.append(targetDesc)
+        sources.append(desc)
+    }
+    var opts = chv_kernel_opts()
+    opts.colorspace = colorspace
+    try check(chv_scale_lanczos_from_yuv_batch(context.handle, &targets, &sources, Int32(pairs.count), &opts))
+    return context
+}
+
 /// An encoder ladder (chv_scale_lanczos_to_yuv_ladder, DESIGN.md section 4.4.3): rungs[r][i] receives what scaleLanczosToYuv(context, src:
 /// srcs[i], target: rungs[r][i]) would write — every rung of every source in one launch per route.  Up to CHV_LADDER_MAX_RUNGS rungs, each with
 /// one target per source; one size per rung, one source size, one format each.

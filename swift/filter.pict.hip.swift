@@ -10,7 +10,8 @@
    scale in one launch) or a separable Lanczos-3 resample: without conversion (BGRA -> BGRA, nv12 -> nv12,
    y420p -> y420p; chv_scale_lanczos, a 4:2:0 picture plane by plane), or BGRA / RGBA -> nv12 / y420p through
    the integer matrix (chv_scale_lanczos_to_yuv), or — only with convert420 — nv12 <-> y420p, the logical planes
-   resampled one by one and stored in the other packing (chv_scale_lanczos_420).
+   resampled one by one and stored in the other packing (chv_scale_lanczos_420), or — only with convertToRgb — nv12 / y420p ->
+   BGRA / RGBA through the integer matrix (chv_scale_lanczos_from_yuv).
    It replaces filter.pict.swift when GPGPU_HIP is defined.
 */
 #if GPGPU_HIP
@@ -31,6 +32,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                 integerMatrix: Bool = true,
                 colorspace: Int32 = 0,
                 convert420: Bool = false,
+                convertToRgb: Bool = false,
                 computeContext: ComputeContext? = nil) {
         self.clock = clock
         self.outputSize = outputSize
@@ -39,6 +41,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
         self.integerMatrix = integerMatrix
         self.colorspace = colorspace
         self.convert420 = convert420
+        self.convertToRgb = convertToRgb
         do {
             if let context = computeContext {
                 self.context = createComputeContext(sharing: context)
@@ -72,6 +75,9 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                         let yuvIn = src.pixelFormat() == .nv12 || src.pixelFormat() == .y420p
                         if strongSelf.convert420 && yuvIn && (format == .nv12 || format == .y420p) && src.pixelFormat() != format {
                             return try scaleLanczos420($0, src: src, target: dst)
+                        }
+                        if strongSelf.convertToRgb && yuvIn && (format == .BGRA || format == .RGBA) {
+                            return try scaleLanczosFromYuv($0, src: src, target: dst, colorspace: strongSelf.colorspace)
                         }
                         guard src.pixelFormat() == format, format == .BGRA || format == .nv12 || format == .y420p else {
                             throw ComputeError.notImplemented
@@ -136,6 +142,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
     let integerMatrix: Bool
     let colorspace: Int32      // chv_colorspace of the integer matrix (the Lanczos conversion)
     let convert420: Bool       // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
+    let convertToRgb: Bool     // the Lanczos scaler takes nv12 / y420p -> BGRA / RGBA (off: the pair is an error, as it was)
     var context: ComputeContext?
 }
 #endif

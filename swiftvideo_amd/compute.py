@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -874,6 +874,37 @@ def scaleLanczos420Ladder(ctx, rungs, srcs):
 
 
 # ---- pipeline operators -----------------------------------------------------------------------
+def scaleLanczosFromYuv(ctx, dst, src, colorspace=cv.CSC_BT601_LIMITED):
+    """Lanczos-3 resize of the nv12 or y420p picture `src` into one BGRA or RGBA plane `dst`, in one launch (chv_scale_lanczos_from_yuv,
+    DESIGN.md section 4.4.6): Y, Cb and Cr are each resampled to dst's size as scaleLanczos resamples a 1-component plane, rounded to codes
+    and taken through the integer matrix of `colorspace` — the decoder side's rendition."""
+    d, s = _image_desc(dst), _image_desc(src)
+    if d is None:
+        raise ComputeError(4, "target has no GPU image buffer")
+    if s is None:
+        raise ComputeError(5, "Bad input image")
+    opts = cv.KernelOpts(colorspace=int(colorspace))
+    cv.check(cv.load().chv_scale_lanczos_from_yuv(ctx.handle, C.byref(d), C.byref(s), C.byref(opts)))
+    return ctx
+
+
+class LanczosFromYuvBatch(LanczosToYuvBatch):
+    """n conversions of one geometry, one source format, one target format and one colourspace issued as one launch per 83 nv12 or 62
+    y420p pictures (chv_scale_lanczos_from_yuv_batch): the previews of several decoded streams per tick.  pairs: [(dst PictureSample, src
+    PictureSample)]; the descriptors are built once, `run` can be called every tick."""
+
+    def run(self, ctx):
+        if self.n == 0:          # an empty list is a no-op, as LanczosBatch's
+            return ctx
+        cv.check(cv.load().chv_scale_lanczos_from_yuv_batch(ctx.handle, self._d, self._s, self.n, C.byref(self._opts)))
+        return ctx
+
+
+def scaleLanczosFromYuvBatch(ctx, pairs, colorspace=cv.CSC_BT601_LIMITED):
+    """[(dst, src)] of one geometry and one format pair in one launch per chunk: the bytes of scaleLanczosFromYuv pair by pair."""
+    return LanczosFromYuvBatch(pairs, colorspace).run(ctx)
+
+
 class GPUBarrierUpload:
     """Tx<PictureSample, PictureSample>, compute.swift:175-198: owns a context sharing
     the given one; passes GPU samples through; errors become ("error", EventError-like)."""
@@ -914,18 +945,19 @@ class PictureFilter:
     composite kernels: colour conversion + bilinear scale in one launch (`scaler="bilinear"`, any format
     pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p
     without a conversion, a 4:2:0 picture plane by plane; BGRA or RGBA -> nv12 or y420p through the integer matrix, scaleLanczosToYuv;
-    with `convert420=True` also nv12 <-> y420p, scaleLanczos420 — off by default: a host that did not ask for a repack gets the error it got).
+    with `convert420=True` also nv12 <-> y420p, scaleLanczos420, and with `convertToRgb=True` also nv12 or y420p -> BGRA or RGBA through the
+    integer matrix, scaleLanczosFromYuv — both off by default: a host that did not ask for a conversion gets the error it got).
     CPU samples are uploaded first; the sample's time stamps, ids and transform state are carried over.
     Results land in a ring of `numberBackingImages` device images like the mixer's (mix.video.swift:148-167)."""
 
     numberBackingImages = 10
 
     def __init__(self, outputSize, outputFormat=PixelFormat.BGRA, computeContext=None, scaler="bilinear",
-                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False):
+                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False, convertToRgb=False):
         """integerMatrix: an RGB picture converted to a 4:2:0 format goes through the integer BT.601/709 matrix of `colorspace`
         (img_*_int, DESIGN.md 4.5: what an encoder expects); False selects the reference's own float kernels (img_bgra_nv12 ...,
         full range, kernels.cl.swift:96-99)."""
-        self.integerMatrix, self.convert420 = integerMatrix, convert420
+        self.integerMatrix, self.convert420, self.convertToRgb = integerMatrix, convert420, convertToRgb
         if scaler not in ("bilinear", "lanczos"):
             raise ComputeError(0, f"unknown scaler {scaler!r}")
         try:
@@ -970,6 +1002,9 @@ class PictureFilter:
                 scaleLanczosToYuv(ctx, dst, src, self.colorspace)       # (the float full-range matrix has no Lanczos form)
             elif self.scaler == "lanczos" and self.convert420 and {src.pixelFormat(), self.outputFormat} == {PixelFormat.nv12, PixelFormat.y420p}:
                 scaleLanczos420(ctx, dst, src)
+            elif self.scaler == "lanczos" and self.convertToRgb and src.pixelFormat() in (PixelFormat.nv12, PixelFormat.y420p) \
+                    and self.outputFormat in (PixelFormat.BGRA, PixelFormat.RGBA):
+                scaleLanczosFromYuv(ctx, dst, src, self.colorspace)
             elif self.scaler == "lanczos":
                 if src.pixelFormat() != self.outputFormat or self.outputFormat not in (PixelFormat.BGRA, PixelFormat.nv12, PixelFormat.y420p):
                     raise ComputeError(9, "lanczos: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p only")

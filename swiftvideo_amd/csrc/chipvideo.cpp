@@ -31,6 +31,7 @@
 #include "lanczos_ladder.h"
 #include "lanczos_planar_ladder.h"
 #include "lanczos_420.h"
+#include "lanczos_from_yuv.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -132,6 +133,9 @@ void chv::register_lanczos_planar_ladder_launcher(LanczosPlanarLadderLauncher fn
 // and for the cross pairs of chv_scale_lanczos_420 / chv_scale_lanczos_420_ladder (lanczos_420.h, kernels_lanczos_420.hip.cpp)
 static std::atomic<Lanczos420Launcher> g_lanczos_420_launcher{nullptr};
 void chv::register_lanczos_420_launcher(Lanczos420Launcher fn) { g_lanczos_420_launcher.store(fn, std::memory_order_release); }
+// and for chv_scale_lanczos_from_yuv / chv_scale_lanczos_from_yuv_batch (lanczos_from_yuv.h, kernels_lanczos_from_yuv.hip.cpp)
+static std::atomic<LanczosFromYuvLauncher> g_lanczos_from_yuv_launcher{nullptr};
+void chv::register_lanczos_from_yuv_launcher(LanczosFromYuvLauncher fn) { g_lanczos_from_yuv_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -155,6 +159,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "stream_f32tap_launches")) { *value = debug_counters().stream_f32tap_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_from_yuv_launches")) { *value = debug_counters().lanczos_from_yuv_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;
@@ -2840,6 +2845,146 @@ extern "C" int chv_scale_lanczos_420(chv_context *c, const chv_image *dst, const
     if (rc) return rc;
     // a same-format pair is chv_scale_lanczos's; a cross pair is the ladder of one rung and one picture
     return dnp == snp ? chv_scale_lanczos(c, dst, src) : chv_scale_lanczos_420_ladder(c, dst, 1, src, 1);
+}
+
+// ---- chv_scale_lanczos_from_yuv: an NV12 or y420p picture -> one BGRA / RGBA plane ----
+// Pictures per descriptor slot of a batch chunk: a picture's target plane and its source planes must fit one slot together — the counts of
+// chv_scale_lanczos_to_yuv_batch, whose pictures have as many plane records.
+static constexpr int kLanczosFromYuvChunkNV12 = kLanczosToYuvChunkNV12, kLanczosFromYuvChunkY420P = kLanczosToYuvChunkY420P;
+static_assert(kLanczosFromYuvChunkNV12 == 83 && kLanczosFromYuvChunkY420P == 62, "include/chipvideo.h states the counts");
+
+// DESIGN.md section 4.2's table (the device's copy is kCsc, pixel_math.hip.h): yoff, cy, crv, cgu, cgv, cbu
+static const int32_t kY2RHost[4][6] = {
+    { 16, 76309, 104597, 25675, 53279, 132201 },  // BT.601 limited
+    { 16, 76309, 117489, 13975, 34925, 138438 },  // BT.709 limited
+    { 0, 65536, 91881, 22553, 46802, 116130 },    // BT.601 full
+    { 0, 65536, 103206, 12276, 30679, 121609 },   // BT.709 full
+};
+
+// (dst, src) of one picture -> its target plane at out[0], its np source planes at out[1 .. np]; every check of plane_to_device
+static int lanczos_from_yuv_planes(chv_context *c, const chv_image *dst, const chv_image *src, int idx, DPlane *out, int *np) {
+    if (!dst || dst->n_planes != 1 || (dst->format != CHV_FMT_BGRA && dst->format != CHV_FMT_RGBA))
+        return fail(CHV_ERR_BAD_TARGET, "Lanczos from YUV: target %d must be one 4-component plane of format BGRA or RGBA", idx);
+    int rc = plane_to_device(dst->planes[0], 4, c->device, &out[0], CHV_ERR_BAD_TARGET, "target", 0);
+    if (rc) return rc;
+    *np = lanczos_planar_planes(src);
+    if (!*np) return fail(CHV_ERR_BAD_INPUT, "Lanczos from YUV: source %d must be nv12 with 2 planes or y420p with 3", idx);
+    for (int p = 0; p < *np; p++) {
+        rc = plane_to_device(src->planes[p], lanczos_planar_comps(src->format, p), c->device, &out[1 + p], CHV_ERR_BAD_INPUT, "input", p);
+        if (rc) return rc;
+        if (p && (out[1 + p].w != std::max(1, out[1].w / 2) || out[1 + p].h != std::max(1, out[1].h / 2)))
+            return fail(CHV_ERR_BAD_INPUT, "Lanczos from YUV: source %d, plane %d is %dx%d, a %dx%d picture's chroma is %dx%d", idx, p, out[1 + p].w,
+                        out[1 + p].h, out[1].w, out[1].h, std::max(1, out[1].w / 2), std::max(1, out[1].h / 2));
+    }
+    return CHV_OK;
+}
+
+// the four tables of one geometry (held in refs until the launch is enqueued) and everything else of the job but the batch
+static int lanczos_from_yuv_job(chv_context *c, const DPlane *planes, int np, int dst_format, const chv_kernel_opts *opts, LanczosRef *refs,
+                                LanczosFromYuvJob *job) {
+    memset(job, 0, sizeof *job);
+    for (int p = 0; p < 2; p++) {
+        const DPlane &s = planes[1 + p];
+        int rc = lanczos_table(c, s.w, planes[0].w, &refs[2 * p]);
+        if (rc) return rc;
+        rc = lanczos_table(c, s.h, planes[0].h, &refs[2 * p + 1]);
+        if (rc) return rc;
+        const LanczosTable &tx = *refs[2 * p], &ty = *refs[2 * p + 1];
+        (p ? job->chroma : job->luma) = LanczosPlaneTables{ tx.first, tx.weights, ty.first, ty.weights, tx.taps, ty.taps };
+    }
+    job->dst = planes[0];
+    for (int p = 0; p < np; p++) job->src[p] = planes[1 + p];
+    job->src_planes = np;
+    job->rgba = dst_format == CHV_FMT_RGBA;
+    const int32_t *k = kY2RHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
+    job->yoff = k[0]; job->cy = k[1]; job->crv = k[2]; job->cgu = k[3]; job->cgv = k[4]; job->cbu = k[5];
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_from_yuv(chv_context *c, const chv_image *dst, const chv_image *src, const chv_kernel_opts *opts) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    const LanczosFromYuvLauncher launcher = g_lanczos_from_yuv_launcher.load(std::memory_order_acquire);
+    DPlane planes[1 + kLanczosPlanarMaxPlanes];
+    DepScope deps;
+    int np = 0;
+    int rc = lanczos_from_yuv_planes(c, dst, src, 0, planes, &np);
+    if (rc) return rc;
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    LanczosRef refs[4];      // held until the launch is enqueued (see LanczosTable)
+    LanczosFromYuvJob job;
+    rc = lanczos_from_yuv_job(c, planes, np, dst->format, opts, refs, &job);
+    if (rc) return rc;
+    job.batch = nullptr; job.n_pictures = 1;
+    (void)hipGetLastError();
+    hipError_t e = launcher(job, c->stream);
+    if (e != hipSuccess) return hip_fail(e, "lanczos from YUV launch");
+    debug_counters().lanczos_from_yuv_launches.fetch_add(1, std::memory_order_relaxed);
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_from_yuv_batch(chv_context *c, const chv_image *dsts, const chv_image *srcs, int n, const chv_kernel_opts *opts) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n == 0) return CHV_OK;
+    if (n < 0 || !dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad batch");
+    const LanczosFromYuvLauncher launcher = g_lanczos_from_yuv_launcher.load(std::memory_order_acquire);
+    // (one target format and one source format per batch: the list's mistake, not the image's — before anything else is looked at)
+    for (int i = 1; i < n; i++) {
+        if (dsts[i].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "target %d has format %d, the batch began with %d (one target format per batch)", i, dsts[i].format, dsts[0].format);
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the batch began with %d (one source format per batch)", i, srcs[i].format, srcs[0].format);
+    }
+    DPlane first[1 + kLanczosPlanarMaxPlanes];
+    DepScope deps;
+    int np = 0;
+    int rc = lanczos_from_yuv_planes(c, &dsts[0], &srcs[0], 0, first, &np);
+    if (rc) return rc;
+    const size_t per = (size_t)np + 1;
+    std::vector<DPlane> planes(per * n);
+    std::copy(first, first + per, planes.begin());
+    for (int i = 1; i < n; i++) {
+        DPlane pi[1 + kLanczosPlanarMaxPlanes];
+        int npi = 0;
+        rc = lanczos_from_yuv_planes(c, &dsts[i], &srcs[i], i, pi, &npi);
+        if (rc) return rc;
+        if (npi != np) return fail(CHV_ERR_INVALID_VALUE, "source %d has %d planes, the batch began with %d (one source format per batch)", i, npi, np);
+        if (pi[0].w != first[0].w || pi[0].h != first[0].h || pi[1].w != first[1].w || pi[1].h != first[1].h)
+            return fail(CHV_ERR_INVALID_VALUE, "pair %d: %dx%d -> %dx%d, the batch is %dx%d -> %dx%d (one geometry per batch)", i,
+                        pi[1].w, pi[1].h, pi[0].w, pi[0].h, first[1].w, first[1].h, first[0].w, first[0].h);
+        std::copy(pi, pi + per, planes.begin() + per * i);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    LanczosRef refs[4];
+    LanczosFromYuvJob job;
+    rc = lanczos_from_yuv_job(c, planes.data(), np, dsts[0].format, opts, refs, &job);
+    if (rc) return rc;
+    // the planes travel through the pinned, device-mapped descriptor ring (a slot per chunk), like chv_scale_lanczos_to_yuv_batch's
+    const int per_slot = np == 2 ? kLanczosFromYuvChunkNV12 : kLanczosFromYuvChunkY420P;
+    for (int at = 0; at < n; at += per_slot) {
+        const int m = std::min(per_slot, n - at);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * at, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        hipError_t e = launcher(job, c->stream);
+        if (e != hipSuccess) return hip_fail(e, "lanczos from YUV launch");
+        debug_counters().lanczos_from_yuv_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    return CHV_OK;
 }
 
 // ---------------------------------------------------------------------------
