@@ -76,7 +76,9 @@ int chv_debug_set_switch(const char *name, const char *value);
  * chv_scale_lanczos_ladder (process-wide), and "lanczos_420_ladder_launches", the same count for the cross-format path (NV12 -> y420p,
  * y420p -> NV12) of chv_scale_lanczos_420 and chv_scale_lanczos_420_ladder (process-wide; same-format pairs through those entries are forwarded
  * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to), and "lanczos_from_yuv_launches", the device
- * launches made by chv_scale_lanczos_from_yuv and chv_scale_lanczos_from_yuv_batch (process-wide: one per call, one per chunk).
+ * launches made by chv_scale_lanczos_from_yuv and chv_scale_lanczos_from_yuv_batch (process-wide: one per call, one per chunk), and
+ * "lanczos_from_yuv_ladder_launches", the device launches made by chv_scale_lanczos_from_yuv_ladder (process-wide: one per chunk for a ladder
+ * whose rungs all take one route, two for one with rungs on both; that entry does not touch "lanczos_from_yuv_launches").
  * Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
@@ -540,6 +542,28 @@ int chv_scale_lanczos_from_yuv(chv_context *ctx, const chv_image *dst, const chv
  * nothing; every other error as above; n == 0 is a no-op.  A chunk is what fits one descriptor slot, counted as chv_scale_lanczos_to_yuv_batch
  * counts it: 83 pictures from NV12 (3 plane records each) or 62 from y420p (4 plane records each). */
 int chv_scale_lanczos_from_yuv_batch(chv_context *ctx, const chv_image *dsts, const chv_image *srcs, int n, const chv_kernel_opts *opts);
+/* The decoder side's LADDER: n_rungs BGRA or RGBA renditions of each of n NV12 or y420p sources, all of them in one
+ * launch per route.  dsts[r * n + i] is rung r of source i; the call writes the bytes of n_rungs x n calls of
+ * chv_scale_lanczos_from_yuv(ctx, &dsts[r * n + i], &srcs[i], opts).  All sources have one size and one format, all targets one format, all
+ * targets of one rung one size; rungs may have any sizes (reductions, 1:1, enlargements, the size of another rung).  One colourspace per call
+ * (opts == NULL: BT.601 limited).  Stream order, upload dependencies, a pass's held work and table lifetime are those of
+ * chv_scale_lanczos_from_yuv_batch.  Every rung of every picture is validated, and every rung's route and launch numbers are computed, before
+ * the first launch: a refused ladder launches nothing and writes nothing to any rung.
+ *   - n_rungs == 0 or n == 0                                                                                   -> no-op, CHV_OK;
+ *   - n_rungs < 0, n_rungs > CHV_LADDER_MAX_RUNGS, n < 0, a NULL list with non-zero counts                      -> CHV_ERR_INVALID_VALUE;
+ *   - targets that differ in format, sources that differ in format or size, a rung whose targets differ in size -> CHV_ERR_INVALID_VALUE;
+ *   - anything else wrong with one picture -> the status chv_scale_lanczos_from_yuv gives it (CHV_ERR_BAD_TARGET, CHV_ERR_BAD_INPUT);
+ *   - a rung with a logical plane that the 160 KB rule of chv_scale_lanczos refuses                             -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation                                                        -> CHV_ERR_NOT_IMPLEMENTED.
+ * A rung takes the route its single call takes; per chunk the strip rungs leave in one launch and the tile rungs in at most one more
+ * ("lanczos_from_yuv_ladder_launches" counts them).  A chunk is what fits one descriptor slot of CHV_LADDER_SLOT_BYTES, a picture being its
+ * n_rungs target planes and its src_planes source planes (stored once) of CHV_LADDER_PLANE_BYTES each:
+ * CHV_FROM_YUV_LADDER_CHUNK(n_rungs, src_planes) pictures, src_planes = 2 for NV12 and 3 for y420p (with one rung: the batch's 83 and 62).  A
+ * longer list is split along the PICTURES: all rungs of a picture leave in one chunk. */
+#define CHV_FROM_YUV_LADDER_CHUNK(n_rungs, src_planes) \
+    (CHV_LADDER_SLOT_BYTES / (((n_rungs) + (src_planes)) * CHV_LADDER_PLANE_BYTES))
+int chv_scale_lanczos_from_yuv_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n,
+                                      const chv_kernel_opts *opts);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

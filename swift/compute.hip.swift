@@ -611,6 +611,33 @@ func scaleLanczosFromYuv(_ context: ComputeContext, pairs: [(src: PictureSample,
     return context
 }
 
+/// The decoder side's ladder (chv_scale_lanczos_from_yuv_ladder, DESIGN.md section 4.4.7): rungs[r][i] receives what scaleLanczosFromYuv(context,
+/// src: srcs[i], target: rungs[r][i]) would write — every BGRA or RGBA rendition of every nv12 or y420p source in one launch per route.  Up to
+/// CHV_LADDER_MAX_RUNGS rungs, each with one target per source; one size per rung, one source size, one format each.
+func scaleLanczosFromYuv(_ context: ComputeContext, srcs: [PictureSample], rungs: [[PictureSample]],
+                         colorspace: Int32 = 0) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for src in srcs {
+        guard let image = src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        sources.append(desc)
+    }
+    for rung in rungs {
+        guard rung.count == srcs.count else { throw ComputeError.invalidValue }
+        for target in rung {
+            guard let targetImage = target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            targets.append(targetDesc)
+        }
+    }
+    var opts = chv_kernel_opts()
+    opts.colorspace = colorspace
+    try check(chv_scale_lanczos_from_yuv_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count), &opts))
+    return context
+}
+
 /// An encoder ladder (chv_scale_lanczos_to_yuv_ladder, DESIGN.md section 4.4.3): rungs[r][i] receives what scaleLanczosToYuv(context, src:
 /// srcs[i], target: rungs[r][i]) would write — every rung of every source in one launch per route.  Up to CHV_LADDER_MAX_RUNGS rungs, each with
 /// one target per source; one size per rung, one source size, one format each.

@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -903,6 +903,24 @@ class LanczosFromYuvBatch(LanczosToYuvBatch):
 def scaleLanczosFromYuvBatch(ctx, pairs, colorspace=cv.CSC_BT601_LIMITED):
     """[(dst, src)] of one geometry and one format pair in one launch per chunk: the bytes of scaleLanczosFromYuv pair by pair."""
     return LanczosFromYuvBatch(pairs, colorspace).run(ctx)
+
+
+class LanczosFromYuvLadder(LanczosToYuvLadder):
+    """The decoder side's ladder (chv_scale_lanczos_from_yuv_ladder): every BGRA or RGBA rendition of every nv12 or
+    y420p source in one launch per route — the rungs that take the wave-per-strip route in one, those that take the tile route in at most one
+    more — with the bytes of the single scaleLanczosFromYuv calls.  rungs: a list of up to 8 rungs, each the list of that rung's targets, one
+    per source (one size per rung, one format for all); srcs: one sample or a list (one size, one format).  The descriptors are built once,
+    `run` can be called every tick."""
+
+    def run(self, ctx):
+        cv.check(cv.load().chv_scale_lanczos_from_yuv_ladder(ctx.handle, self._d, self.n_rungs, self._s, self.n, C.byref(self._opts)))
+        return ctx
+
+
+def scaleLanczosFromYuvLadder(ctx, rungs, srcs, colorspace=cv.CSC_BT601_LIMITED):
+    """Every rendition of one or several decoded pictures of one size, all of them in one launch per route
+    (chv_scale_lanczos_from_yuv_ladder): rungs[r][i] receives what scaleLanczosFromYuv(ctx, rungs[r][i], srcs[i], colorspace) would write."""
+    return LanczosFromYuvLadder(rungs, srcs, colorspace).run(ctx)
 
 
 class GPUBarrierUpload:

@@ -32,6 +32,7 @@
 #include "lanczos_planar_ladder.h"
 #include "lanczos_420.h"
 #include "lanczos_from_yuv.h"
+#include "lanczos_from_yuv_ladder.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -136,6 +137,9 @@ void chv::register_lanczos_420_launcher(Lanczos420Launcher fn) { g_lanczos_420_l
 // and for chv_scale_lanczos_from_yuv / chv_scale_lanczos_from_yuv_batch (lanczos_from_yuv.h, kernels_lanczos_from_yuv.hip.cpp)
 static std::atomic<LanczosFromYuvLauncher> g_lanczos_from_yuv_launcher{nullptr};
 void chv::register_lanczos_from_yuv_launcher(LanczosFromYuvLauncher fn) { g_lanczos_from_yuv_launcher.store(fn, std::memory_order_release); }
+// and for chv_scale_lanczos_from_yuv_ladder (lanczos_from_yuv_ladder.h, kernels_lanczos_from_yuv_ladder.hip.cpp)
+static std::atomic<LanczosFromYuvLadderLauncher> g_lanczos_from_yuv_ladder_launcher{nullptr};
+void chv::register_lanczos_from_yuv_ladder_launcher(LanczosFromYuvLadderLauncher fn) { g_lanczos_from_yuv_ladder_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -160,6 +164,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_launches")) { *value = debug_counters().lanczos_from_yuv_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_from_yuv_ladder_launches")) { *value = debug_counters().lanczos_from_yuv_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;
@@ -2983,6 +2988,102 @@ extern "C" int chv_scale_lanczos_from_yuv_batch(chv_context *c, const chv_image 
         hipError_t e = launcher(job, c->stream);
         if (e != hipSuccess) return hip_fail(e, "lanczos from YUV launch");
         debug_counters().lanczos_from_yuv_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    return CHV_OK;
+}
+
+// ---- chv_scale_lanczos_from_yuv_ladder: every BGRA / RGBA rendition of every decoded picture in one launch per route ----
+// Pictures per descriptor slot: a picture's n_rungs target planes and its source planes (stored once) must fit one slot together.
+// include/chipvideo.h states the rule as CHV_FROM_YUV_LADDER_CHUNK; with one rung it gives the batch's counts.
+static constexpr int lanczos_from_yuv_ladder_chunk(int n_rungs, int snp) { return (int)(kDescSlotBytes / (((size_t)n_rungs + snp) * sizeof(DPlane))); }
+static_assert(lanczos_from_yuv_ladder_chunk(1, 2) == kLanczosFromYuvChunkNV12 && lanczos_from_yuv_ladder_chunk(1, 3) == kLanczosFromYuvChunkY420P &&
+              CHV_FROM_YUV_LADDER_CHUNK(1, 2) == 83 && CHV_FROM_YUV_LADDER_CHUNK(1, 3) == 62 &&
+              lanczos_from_yuv_ladder_chunk(8, 2) == CHV_FROM_YUV_LADDER_CHUNK(8, 2) && lanczos_from_yuv_ladder_chunk(8, 3) == CHV_FROM_YUV_LADDER_CHUNK(8, 3) &&
+              lanczos_from_yuv_ladder_chunk(CHV_LADDER_MAX_RUNGS, 3) >= 1,
+              "a chunk is what fits one descriptor slot (include/chipvideo.h states the rule); one rung is chunked like chv_scale_lanczos_from_yuv_batch");
+
+extern "C" int chv_scale_lanczos_from_yuv_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, const chv_kernel_opts *opts) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
+    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
+    if (n_rungs == 0 || n == 0) return CHV_OK;
+    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    const LanczosFromYuvLadderLauncher launcher = g_lanczos_from_yuv_ladder_launcher.load(std::memory_order_acquire);
+    // (one format per list: the list's mistake, not the image's — before anything else is looked at)
+    for (int k = 1; k < n_rungs * n; k++)
+        if (dsts[k].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
+    for (int i = 1; i < n; i++)
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    // a picture's record: the target plane of rung 0, of rung 1, ..., then the snp source planes
+    const int snp0 = lanczos_planar_planes(&srcs[0]);
+    const int snp = snp0 ? snp0 : 2;                   // (a source that is neither packing is refused below, by its own status)
+    const size_t per = (size_t)n_rungs + snp, src_at = (size_t)n_rungs;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        for (int r = 0; r < n_rungs; r++) {
+            DPlane one[1 + kLanczosPlanarMaxPlanes];
+            int np = 0;
+            int rc = lanczos_from_yuv_planes(c, &dsts[(size_t)r * n + i], &srcs[i], r * n + i, one, &np);
+            if (rc) return rc;
+            if (np != snp) return fail(CHV_ERR_INVALID_VALUE, "source %d has %d planes, the ladder began with %d (one source format per ladder)", i, np, snp);
+            pi[r] = one[0];
+            if (r == 0) std::copy(one + 1, one + 1 + snp, pi + src_at);
+            if (pi[r].w != planes[r].w || pi[r].h != planes[r].h)
+                return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, pi[r].w, pi[r].h,
+                            planes[r].w, planes[r].h);
+        }
+        if (pi[src_at].w != planes[src_at].w || pi[src_at].h != planes[src_at].h)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, pi[src_at].w, pi[src_at].h,
+                        planes[src_at].w, planes[src_at].h);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV ladder kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    // four tables per rung, from the shared cache; every reference is held until the last launch is enqueued
+    LanczosRef refs[4 * CHV_LADDER_MAX_RUNGS];
+    LanczosFromYuvLadderJob job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs; job.src_planes = snp;
+    job.rgba = dsts[0].format == CHV_FMT_RGBA;
+    job.luma_w = planes[src_at].w; job.luma_h = planes[src_at].h;
+    job.chroma_w = planes[src_at + 1].w; job.chroma_h = planes[src_at + 1].h;
+    const int32_t *k = kY2RHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
+    job.yoff = k[0]; job.cy = k[1]; job.crv = k[2]; job.cgu = k[3]; job.cgv = k[4]; job.cbu = k[5];
+    for (int r = 0; r < n_rungs; r++) {
+        LanczosFromYuvLadderRung &R = job.rung[r];
+        R.w = planes[r].w; R.h = planes[r].h;
+        for (int p = 0; p < 2; p++) {
+            LanczosRef &rx = refs[4 * r + 2 * p], &ry = refs[4 * r + 2 * p + 1];
+            rc = lanczos_table(c, p ? job.chroma_w : job.luma_w, R.w, &rx);
+            if (rc) return rc;
+            rc = lanczos_table(c, p ? job.chroma_h : job.luma_h, R.h, &ry);
+            if (rc) return rc;
+            (p ? R.chroma : R.luma) = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
+        }
+    }
+    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES
+    const int per_slot = lanczos_from_yuv_ladder_chunk(n_rungs, snp);
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_from_yuv_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        if (e != hipSuccess) return hip_fail(e, "lanczos from YUV ladder launch");
     }
     return CHV_OK;
 }
