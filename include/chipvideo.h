@@ -70,7 +70,7 @@ int chv_debug_set_switch(const char *name, const char *value);
 /* Measurement / test hook: counters of the current device's store of strip-kernel geometry tables (csrc/geom_cache.h): "geom_store_patched"
  * (launches whose layers were pointed at stored tables before their descriptors travelled: batches at creation, lone ticks),
  * "geom_store_batch_hits", "geom_store_builds", "geom_store_bytes", "geom_store_tables"; and "stream_opaque_launches", the launches of
- * tick_bgra_stream that took the opaque-bottom kernels, and "stream_carry_launches", those of them that took the chroma-carry kernels, "stream_f32tap_launches", those of these that took the f32-tap kernels,
+ * tick_bgra_stream that took the opaque-bottom kernels, and "stream_carry_launches", those of them that took the chroma-carry kernels, "stream_f32tap_launches", those of these that took the f32-tap kernels, and "stream_phased_launches", the launches of tick_bgra_stream cut into more than one phase (csrc/stream_plan.h),
  * (process-wide); and "lanczos_ladder_launches", the device launches made by chv_scale_lanczos_to_yuv_ladder (process-wide: one per chunk for a
  * ladder whose rungs all take one route, two for one with rungs on both), and "lanczos_planar_ladder_launches", the same count for
  * chv_scale_lanczos_ladder (process-wide), and "lanczos_420_ladder_launches", the same count for the cross-format path (NV12 -> y420p,

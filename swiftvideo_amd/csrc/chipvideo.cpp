@@ -95,19 +95,20 @@ static int parse_switch(const char *name, const char *value, int *out) {
     if (n == "CHV_STREAM_CARRY") { *out = v == "0" ? 0 : 1; return 14; }
     if (n == "CHV_REBIND") { *out = v == "scatter" ? 1 : v == "copy" ? 2 : 0; return 13; }
     if (n == "CHV_STREAM_F32TAPS") { *out = v == "0" ? 0 : 1; return 15; }
+    if (n == "CHV_STREAM_PLAN") { const int r = atoi(v.c_str()); *out = v == "0" ? 0 : (r >= 2 && r <= (1 << 24)) ? r : 1; return 16; }
     return -1;
 }
 static void store_switch(Switches &s, int which, int val) {
-    std::atomic<int> *slots[16] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
-                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows, &s.stream_opaque, &s.rebind, &s.stream_carry, &s.stream_f32taps };
+    std::atomic<int> *slots[17] = { &s.force_general, &s.bgra_path, &s.wave_rows, &s.tile_rows, &s.same_geom, &s.desc_host, &s.stream, &s.yuv_stream, &s.wave_dma,
+                                    &s.pass_fuse, &s.geom_cache, &s.stream_rows, &s.stream_opaque, &s.rebind, &s.stream_carry, &s.stream_f32taps, &s.stream_plan };
     slots[which]->store(val, std::memory_order_relaxed);
 }
 Switches &chv::switches() {
     static Switches s;
     static std::once_flag once;
     std::call_once(once, [] {
-        static const char *const names[16] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
-                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS", "CHV_STREAM_OPAQUE", "CHV_REBIND", "CHV_STREAM_CARRY", "CHV_STREAM_F32TAPS" };
+        static const char *const names[17] = { "CHV_FORCE_GENERAL", "CHV_BGRA_PATH", "CHV_WAVE_ROWS", "CHV_TILE_ROWS", "CHV_SAME_GEOM", "CHV_DESC", "CHV_STREAM", "CHV_YUV_STREAM",
+                                               "CHV_WAVE_DMA", "CHV_PASS_FUSE", "CHV_GEOM_CACHE", "CHV_STREAM_ROWS", "CHV_STREAM_OPAQUE", "CHV_REBIND", "CHV_STREAM_CARRY", "CHV_STREAM_F32TAPS", "CHV_STREAM_PLAN" };
         for (const char *n : names) {
             const char *v = getenv(n);
             int val = 0, which = v ? parse_switch(n, v, &val) : -1;
@@ -149,7 +150,7 @@ extern "C" int chv_debug_set_switch(const char *name, const char *value) {
     Switches &s = switches();                     // (environment first, so that a later first use cannot overwrite this)
     const int which = parse_switch(name, value, &val);
     if (which < 0) { g_detail_set("unknown switch"); return CHV_ERR_INVALID_VALUE; }
-    if (!value || !*value) val = (which == 4 || which == 6 || which == 7 || which == 8 || which == 9 || which == 10 || which == 12 || which == 14 || which == 15) ? 1 : 0;      // empty / NULL: back to "the library decides"
+    if (!value || !*value) val = (which == 4 || which == 6 || which == 7 || which == 8 || which == 9 || which == 10 || which == 12 || which == 14 || which == 15 || which == 16) ? 1 : 0;      // empty / NULL: back to "the library decides"
     store_switch(s, which, val);
     return CHV_OK;
 }
@@ -161,6 +162,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "stream_opaque_launches")) { *value = debug_counters().stream_opaque_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_carry_launches")) { *value = debug_counters().stream_carry_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "stream_f32tap_launches")) { *value = debug_counters().stream_f32tap_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "stream_phased_launches")) { *value = debug_counters().stream_phased_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_launches")) { *value = debug_counters().lanczos_from_yuv_launches.load(std::memory_order_relaxed); return CHV_OK; }

@@ -1,9 +1,10 @@
 // kernels_stream_body.hip.inc — stream_body, the device code of the tick_bgra_stream kernels, and what it is built with: included by
 // kernels_stream.hip.cpp (the 32 kernels of every eligible launch), kernels_stream_opq.hip.cpp (the opaque-bottom kernels) and
-// kernels_stream_carry.hip.cpp (the chroma-carry kernels) and kernels_stream_dn.hip.cpp (their f32-tap form), each of which instantiates its own __global__ wrappers.  The kernel's description is at the top of kernels_stream.hip.cpp.
+// kernels_stream_carry.hip.cpp (the chroma-carry kernels) and kernels_stream_dn.hip.cpp (their f32-tap form), each of which instantiates its own __global__ wrappers.  How a launch is cut into waves: stream_plan.h.  The kernel's description is at the top of kernels_stream.hip.cpp.
 #pragma once
 #include "wave_common.hip.h"
 #include "switches.h"
+#include "stream_plan.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -39,6 +40,9 @@ namespace chv {
                                   // short chunks won (neighbouring strips drift apart over a tall chunk and fetch shared lines twice: 240 rows 1.59 ms
                                   // and 1.75x the algorithmic bytes, 30 rows 1.34 ms); with four strips per block and trimmed requests: 3 / 6 / 12 /
                                   // 18 / 24 / 48 rounds (240 .. 16 rows) = 1.294 / 1.256 / 1.250 / 1.276 / 1.282 / 1.347 ms, traffic 1.00x at 60 rows
+                                  // (the six-wave kernel of its day).  The uniform rule only: today's five-wave f32-tap kernel is as flat — 24 / 36 / 52 / 60 / 90 /
+                                  // 120 / 240 / 720 rows = 1.072 / 1.055 / 1.047 / 1.043 / 1.041 / 1.047 / 1.068 / 1.129 ms — and batches that fill the chip
+                                  // several times over leave the rule for a phased plan (stream_plan.h, profiles/stream_plan_notes.md)
 #endif
 #ifndef CHV_STREAM_WAVES
 #define CHV_STREAM_WAVES 6
@@ -172,8 +176,11 @@ CHV_DEV void st_carry_wait(StLuma &t, StCarry<NL> &even, StCarry<NL> &odd) {
 // DN: the taps of the carry form enter full-rate v_fma_f32 / v_fmac_f32 as binary32 denormals instead of v_fma_mix_f32 as binary16 ones
 // (cs_mix_d, pixel_math.hip.h; kernels_stream_dn.hip.cpp): the column weights carry 2^127 where they carry kTapScale, the samples leave the
 // taps scaled by 2^-22 and the 2^22 rides on the add that converts them (yuv_to_bgr_fixed_absorbed_d).  Same bytes; the blend is untouched.
-template <int NL, bool ONE, bool PL, bool ABS, bool OPQ = false, bool CRY = false, bool DN = false>
-CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int n_ticks, int strips_x, int chunks_y, int rows_per_chunk) {
+// CUT, how the launch is cut into waves: a batch's StreamPlan (stream_plan.h: up to four phases of falling chunk heights, a kernel argument read
+// by scalar loads; only tick, y0, nrows and strip live past the prologue), the by-value lone tick's StreamUniform (one grid, its old arguments)
+struct StreamUniform { int chunks_y, rows; };
+template <int NL, bool ONE, bool PL, bool ABS, bool OPQ = false, bool CRY = false, bool DN = false, class CUT>
+CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int strips_x, const CUT &cut) {
     // ST_WAVES independent waves per block, on neighbouring strips (no barrier anywhere): their source windows overlap by a vector or two,
     // and waves of one block start together on one CU — the shared lines are fetched once (HBM traffic 1.47x -> see profiles/r03_notes.md)
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_all[];
@@ -190,18 +197,19 @@ CHV_DEV void stream_body(const DTick *__restrict__ ticks, const DLayer *__restri
     static_assert(!CRY || (OPQ && !PL && !ONE && !(CHV_ST_ABL & 4)), "the chroma-carry form: opaque-bottom batch kernels of NV12 sources");
     static_assert(!DN || CRY, "the f32-tap form: the chroma-carry kernels");
     const int lane = threadIdx.x & 63;
-    // XCD-aware numbering: block b runs on XCD b % 8; an XCD owns a contiguous range of (tick, chunk, group of ST_WAVES strips)
-    const int groups_x = (strips_x + ST_WAVES - 1) / ST_WAVES;
-    const int total = n_ticks * chunks_y * groups_x;
-    const int b = blockIdx.x, per_xcd = (total + 7) >> 3;
-    const int idx = (b & 7) * per_xcd + (b >> 3);
-    if ((b >> 3) >= per_xcd || idx >= total) return;
-    const int tick = idx / (chunks_y * groups_x), rem = idx - tick * (chunks_y * groups_x);
-    const int chunk = rem / groups_x, strip = (rem - chunk * groups_x) * ST_WAVES + wave;
-    if (strip >= strips_x) return;
+    // XCD-aware numbering inside a phase: block b runs on XCD b % 8; an XCD owns a contiguous range of (tick, chunk, group of ST_WAVES strips)
+    int tick, y0, rows_per_chunk, strip;
+    if constexpr (ONE) {
+        static_assert(std::is_same<CUT, StreamUniform>::value, "the by-value lone tick: one uniform grid");
+        rows_per_chunk = cut.rows;
+        if (!stream_phase_decode(0, 1, cut.chunks_y, cut.rows, strips_x, ST_WAVES, (int)blockIdx.x, wave, tick, y0, strip)) return;
+    } else {
+        static_assert(std::is_same<CUT, StreamPlan>::value, "a batch: its plan");
+        if (!stream_plan_decode(cut, strips_x, ST_WAVES, (int)blockIdx.x, wave, tick, y0, rows_per_chunk, strip)) return;
+    }
     const DTick &T = ticks[ONE ? 0 : tick];
     const DLayer *L = layers + (ONE ? 0 : T.first_layer);
-    const int x0 = strip * 64, y0 = chunk * rows_per_chunk;
+    const int x0 = strip * 64;
     if (x0 >= T.W || y0 >= T.H) return;
     const int nrows = min(rows_per_chunk, T.H - y0);
     const DPlane D = T.dst.pl[0];

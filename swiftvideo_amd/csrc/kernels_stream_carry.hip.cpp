@@ -14,20 +14,20 @@ namespace chv {
 #endif
 
 template <int NL>
-__global__ __launch_bounds__(64 * ST_WAVES, CHV_STREAM_CARRY_WAVES) void tick_bgra_stream_cc(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int n_ticks,
-                                                                                   int strips_x, int chunks_y, int rows_per_chunk) {
-    stream_body<NL, false, false, true, true, true>(ticks, layers, n_ticks, strips_x, chunks_y, rows_per_chunk);
+__global__ __launch_bounds__(64 * ST_WAVES, CHV_STREAM_CARRY_WAVES) void tick_bgra_stream_cc(const DTick *__restrict__ ticks, const DLayer *__restrict__ layers, int strips_x,
+                                                                                   const StreamPlan plan) {
+    stream_body<NL, false, false, true, true, true>(ticks, layers, strips_x, plan);
 }
 
 // a batch launch (descriptors on the device) of `nl` = 2 .. 4 NV12 layers with absorbed matrices and opaque bottoms; grid, LDS and arguments
 // are those of the kernels it replaces
-hipError_t launch_bgra_stream_carry(int nl, const DTick *ticks, const DLayer *layers, int n_ticks, dim3 grid, size_t lds, int strips_x, int chunks_y, int rows,
+hipError_t launch_bgra_stream_carry(int nl, const DTick *ticks, const DLayer *layers, int n_ticks, dim3 grid, size_t lds, int strips_x, const StreamPlan &plan,
                                     hipStream_t stream) {
     if (!ticks || !layers) return hipErrorInvalidValue;
     switch (nl) {
-    case 2: hipLaunchKernelGGL((tick_bgra_stream_cc<2>), grid, dim3(64 * ST_WAVES), lds, stream, ticks, layers, n_ticks, strips_x, chunks_y, rows); break;
-    case 3: hipLaunchKernelGGL((tick_bgra_stream_cc<3>), grid, dim3(64 * ST_WAVES), lds, stream, ticks, layers, n_ticks, strips_x, chunks_y, rows); break;
-    case 4: hipLaunchKernelGGL((tick_bgra_stream_cc<4>), grid, dim3(64 * ST_WAVES), lds, stream, ticks, layers, n_ticks, strips_x, chunks_y, rows); break;
+    case 2: hipLaunchKernelGGL((tick_bgra_stream_cc<2>), grid, dim3(64 * ST_WAVES), lds, stream, ticks, layers, strips_x, plan); break;
+    case 3: hipLaunchKernelGGL((tick_bgra_stream_cc<3>), grid, dim3(64 * ST_WAVES), lds, stream, ticks, layers, strips_x, plan); break;
+    case 4: hipLaunchKernelGGL((tick_bgra_stream_cc<4>), grid, dim3(64 * ST_WAVES), lds, stream, ticks, layers, strips_x, plan); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -2,7 +2,7 @@
 //
 // The environment is read ONCE, at the first use in the process (getenv on a hot path is undefined behaviour next to a
 // setenv in another thread, and the mixer and uploader threads run concurrently): CHV_FORCE_GENERAL, CHV_BGRA_PATH,
-// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE, CHV_STREAM_CARRY, CHV_STREAM_F32TAPS, CHV_REBIND.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
+// CHV_WAVE_ROWS, CHV_TILE_ROWS, CHV_SAME_GEOM, CHV_DESC, CHV_STREAM, CHV_YUV_STREAM, CHV_WAVE_DMA, CHV_PASS_FUSE, CHV_GEOM_CACHE, CHV_STREAM_ROWS, CHV_STREAM_OPAQUE, CHV_STREAM_CARRY, CHV_STREAM_F32TAPS, CHV_STREAM_PLAN, CHV_REBIND.  Tests and A/B tools change them afterwards through chv_debug_set_switch (include/chipvideo.h),
 // never through the environment.  Every value is an atomic int; 0 = "the library decides".
 #pragma once
 #include <atomic>
@@ -38,6 +38,10 @@ struct Switches {
     std::atomic<int> stream_f32taps{1};  // CHV_STREAM_F32TAPS: 0 chroma-carry launches keep the kernels whose taps are v_fma_mix_f32 (A/B and parity tests); 1 (default)
                                          // they take the kernels whose taps are f32 multiply-adds on binary32 denormals (kernels_stream_dn.hip.cpp;
                                          // profiles/f32_denormal_taps_notes.md)
+    std::atomic<int> stream_plan{1};     // CHV_STREAM_PLAN, how a batch launch of tick_bgra_stream is cut into waves (stream_plan.h): 0 one uniform chunk height always
+                                         // (A/B and parity tests); 1 (default) batches whose tall phase alone fills the chip once run tall chunks first and short
+                                         // ones at the end (profiles/stream_plan_notes.md); N >= 2 (tests) plan as if the chip held N waves and a tenth of a
+                                         // round were enough, so that a batch of a few small ticks gets several phases
     std::atomic<int> rebind{0};          // CHV_REBIND, how chv_batch_rebind sends the new plane addresses: scatter (1) the scatter kernel (kernels_rebind.hip.cpp)
                                          // wherever the batch has a pooled block and the unit is linked; copy (2) the whole descriptor block again (A/B, and
                                          // the only way without them); 0 (default) the library decides (profiles/batch_rebind_notes.md)
@@ -50,6 +54,7 @@ struct DebugCounters {
     std::atomic<unsigned long long> stream_opaque_launches{0};       // launches of tick_bgra_stream that took the opaque-bottom kernels
     std::atomic<unsigned long long> stream_carry_launches{0};        // ... of which: the chroma-carry kernels (kernels_stream_carry.hip.cpp)
     std::atomic<unsigned long long> stream_f32tap_launches{0};       // ... of which: the f32-tap kernels (kernels_stream_dn.hip.cpp)
+    std::atomic<unsigned long long> stream_phased_launches{0};       // launches of tick_bgra_stream cut into more than one phase (stream_plan.h)
     std::atomic<unsigned long long> lanczos_ladder_launches{0};      // device launches made by chv_scale_lanczos_to_yuv_ladder
     std::atomic<unsigned long long> lanczos_planar_ladder_launches{0};      // device launches made by chv_scale_lanczos_ladder
     std::atomic<unsigned long long> lanczos_420_ladder_launches{0};         // device launches made by the cross-format path of chv_scale_lanczos_420 / _420_ladder
