@@ -78,7 +78,8 @@ int chv_debug_set_switch(const char *name, const char *value);
  * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to), and "lanczos_from_yuv_launches", the device
  * launches made by chv_scale_lanczos_from_yuv and chv_scale_lanczos_from_yuv_batch (process-wide: one per call, one per chunk), and
  * "lanczos_from_yuv_ladder_launches", the device launches made by chv_scale_lanczos_from_yuv_ladder (process-wide: one per chunk for a ladder
- * whose rungs all take one route, two for one with rungs on both; that entry does not touch "lanczos_from_yuv_launches").
+ * whose rungs all take one route, two for one with rungs on both; that entry does not touch "lanczos_from_yuv_launches"), and
+ * "lanczos_rgb_ladder_launches", the same count for chv_scale_lanczos_rgb_ladder (process-wide; that entry touches no other counter).
  * Unknown name -> CHV_ERR_INVALID_VALUE. */
 int chv_debug_get_counter(const char *name, unsigned long long *value);
 
@@ -564,6 +565,30 @@ int chv_scale_lanczos_from_yuv_batch(chv_context *ctx, const chv_image *dsts, co
     (CHV_LADDER_SLOT_BYTES / (((n_rungs) + (src_planes)) * CHV_LADDER_PLANE_BYTES))
 int chv_scale_lanczos_from_yuv_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n,
                                       const chv_kernel_opts *opts);
+/* The LADDER of 4-component planes: n_rungs renditions of each of n BGRA or RGBA planes — the canvases
+ * tick_bgra_stream writes, for one — all of them in one launch per route.  dsts[r * n + i] is rung r of source i; the call writes the bytes of
+ * n_rungs x n calls of chv_scale_lanczos(ctx, &dsts[r * n + i], &srcs[i]) on one 4-component plane each.  All sources have one size, all
+ * targets of one rung one size; rungs may have any sizes (reductions, 1:1, enlargements, the size of another rung).  The `format` field of a
+ * 4-component image is not read, as in chv_scale_lanczos: bytes keep their component order.  Stream order, upload dependencies, a pass's
+ * held work and table lifetime are those of chv_scale_lanczos_batch.  Every rung of every picture is validated, and every rung's route and
+ * launch numbers are computed, before the first launch: a refused ladder launches nothing and writes nothing to any rung.
+ *   - n_rungs == 0 or n == 0                                                                                   -> no-op, CHV_OK;
+ *   - n_rungs < 0, n_rungs > CHV_LADDER_MAX_RUNGS, n < 0, a NULL list with non-zero counts                      -> CHV_ERR_INVALID_VALUE;
+ *   - a target that is not exactly one plane of 4 components (a 4:2:0 picture included: this entry has only the 4-component family), or
+ *     whose plane fails a check of chv_scale_lanczos                                                           -> CHV_ERR_BAD_TARGET;
+ *   - the same conditions on a source                                                                          -> CHV_ERR_BAD_INPUT;
+ *   - sources that differ in size, a rung whose targets differ in size                                         -> CHV_ERR_INVALID_VALUE;
+ *   - a rung that chv_scale_lanczos refuses for the same sizes (its 160 KB rule, more than 256 taps)            -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation                                                        -> CHV_ERR_NOT_IMPLEMENTED.
+ * The route is a function of a rung's geometry alone, and not the single call's: a rung takes the wave-per-strip route when neither axis has
+ * more than 22 taps, the source is at least 4 texels wide and the staged row of a strip fits 64 vectors — also where its axes have different
+ * tap counts, which a single call sends to its tile kernel — and the tile route otherwise.  Per chunk the strip rungs leave in one launch and
+ * the tile rungs in at most one more ("lanczos_rgb_ladder_launches" counts them).  A chunk is what fits one descriptor slot of
+ * CHV_LADDER_SLOT_BYTES, a picture being its n_rungs target planes and its one source plane (stored once) of CHV_LADDER_PLANE_BYTES each:
+ * CHV_RGB_LADDER_CHUNK(n_rungs) pictures (124 with one rung, 27 with eight).  A longer list is split along the PICTURES: all rungs of a
+ * picture leave in one chunk. */
+#define CHV_RGB_LADDER_CHUNK(n_rungs) (CHV_LADDER_SLOT_BYTES / (((n_rungs) + 1) * CHV_LADDER_PLANE_BYTES))
+int chv_scale_lanczos_rgb_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
 
 /* ---- timing (what the "gpu.upload"/"mix.video.compose" StatsReport timers
  *      measure on the host, compute.swift:185-187, mix.video.swift:110-126,

@@ -638,6 +638,30 @@ func scaleLanczosFromYuv(_ context: ComputeContext, srcs: [PictureSample], rungs
     return context
 }
 
+/// The ladder of 4-component planes (chv_scale_lanczos_rgb_ladder, DESIGN.md section 4.4.8): rungs[r][i] receives what scaleLanczos would write
+/// for the BGRA or RGBA pair (srcs[i], rungs[r][i]) — every rendition of every source in one launch per route.  Up to CHV_LADDER_MAX_RUNGS
+/// rungs, each with one target per source; one size per rung, one source size; bytes keep their component order.
+func scaleLanczosRgb(_ context: ComputeContext, srcs: [PictureSample], rungs: [[PictureSample]]) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for src in srcs {
+        guard let image = src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        sources.append(desc)
+    }
+    for rung in rungs {
+        guard rung.count == srcs.count else { throw ComputeError.invalidValue }
+        for target in rung {
+            guard let targetImage = target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            targets.append(targetDesc)
+        }
+    }
+    try check(chv_scale_lanczos_rgb_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
+    return context
+}
+
 /// An encoder ladder (chv_scale_lanczos_to_yuv_ladder, DESIGN.md section 4.4.3): rungs[r][i] receives what scaleLanczosToYuv(context, src:
 /// srcs[i], target: rungs[r][i]) would write — every rung of every source in one launch per route.  Up to CHV_LADDER_MAX_RUNGS rungs, each with
 /// one target per source; one size per rung, one source size, one format each.

@@ -141,6 +141,7 @@ _SIGNATURES = {
     "chv_scale_lanczos_from_yuv": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.POINTER(KernelOpts)]),
     "chv_scale_lanczos_from_yuv_batch": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.c_int, C.POINTER(KernelOpts)]),
     "chv_scale_lanczos_from_yuv_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int, C.POINTER(KernelOpts)]),
+    "chv_scale_lanczos_rgb_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
     "chv_custom_prelude": (C.c_char_p, []),
     "chv_kernel_build": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
     "chv_run_custom": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(Image), C.POINTER(Image), C.c_int, C.c_void_p,

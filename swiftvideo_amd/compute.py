@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "scaleLanczosRgbLadder", "LanczosRgbLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -921,6 +921,23 @@ def scaleLanczosFromYuvLadder(ctx, rungs, srcs, colorspace=cv.CSC_BT601_LIMITED)
     """Every rendition of one or several decoded pictures of one size, all of them in one launch per route
     (chv_scale_lanczos_from_yuv_ladder): rungs[r][i] receives what scaleLanczosFromYuv(ctx, rungs[r][i], srcs[i], colorspace) would write."""
     return LanczosFromYuvLadder(rungs, srcs, colorspace).run(ctx)
+
+
+class LanczosRgbLadder(LanczosLadder):
+    """The ladder of 4-component planes (chv_scale_lanczos_rgb_ladder): every rendition of every BGRA or RGBA source —
+    the canvases of the compositing tick, for one — in one launch per route, with the bytes of the single scaleLanczos calls.  rungs: a list
+    of up to 8 rungs, each the list of that rung's targets, one per source (one size per rung); srcs: one sample or a list (one size).  Bytes
+    keep their component order.  The descriptors are built once, `run` can be called every tick."""
+
+    def run(self, ctx):
+        cv.check(cv.load().chv_scale_lanczos_rgb_ladder(ctx.handle, self._d, self.n_rungs, self._s, self.n))
+        return ctx
+
+
+def scaleLanczosRgbLadder(ctx, rungs, srcs):
+    """Every rendition of one or several BGRA or RGBA pictures of one size, all of them in one launch per route
+    (chv_scale_lanczos_rgb_ladder): rungs[r][i] receives what scaleLanczos(ctx, rungs[r][i], srcs[i]) would write."""
+    return LanczosRgbLadder(rungs, srcs).run(ctx)
 
 
 class GPUBarrierUpload:

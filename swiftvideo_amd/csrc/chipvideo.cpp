@@ -33,6 +33,7 @@
 #include "lanczos_420.h"
 #include "lanczos_from_yuv.h"
 #include "lanczos_from_yuv_ladder.h"
+#include "lanczos_rgb_ladder.h"
 
 namespace chv {
 const char *bgra_wave_build_flags();      // kernels_wave.hip.cpp
@@ -141,6 +142,9 @@ void chv::register_lanczos_from_yuv_launcher(LanczosFromYuvLauncher fn) { g_lanc
 // and for chv_scale_lanczos_from_yuv_ladder (lanczos_from_yuv_ladder.h, kernels_lanczos_from_yuv_ladder.hip.cpp)
 static std::atomic<LanczosFromYuvLadderLauncher> g_lanczos_from_yuv_ladder_launcher{nullptr};
 void chv::register_lanczos_from_yuv_ladder_launcher(LanczosFromYuvLadderLauncher fn) { g_lanczos_from_yuv_ladder_launcher.store(fn, std::memory_order_release); }
+// and for chv_scale_lanczos_rgb_ladder (lanczos_rgb_ladder.h, kernels_lanczos_rgb_ladder.hip.cpp)
+static std::atomic<LanczosRgbLadderLauncher> g_lanczos_rgb_ladder_launcher{nullptr};
+void chv::register_lanczos_rgb_ladder_launcher(LanczosRgbLadderLauncher fn) { g_lanczos_rgb_ladder_launcher.store(fn, std::memory_order_release); }
 DebugCounters &chv::debug_counters() {
     static DebugCounters c;
     return c;
@@ -167,6 +171,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_launches")) { *value = debug_counters().lanczos_from_yuv_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_ladder_launches")) { *value = debug_counters().lanczos_from_yuv_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_rgb_ladder_launches")) { *value = debug_counters().lanczos_rgb_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_ladder_launches")) { *value = debug_counters().lanczos_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     g_detail_set("unknown counter");
     return CHV_ERR_INVALID_VALUE;
@@ -3086,6 +3091,88 @@ extern "C" int chv_scale_lanczos_from_yuv_ladder(chv_context *c, const chv_image
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_from_yuv_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
         if (e != hipSuccess) return hip_fail(e, "lanczos from YUV ladder launch");
+    }
+    return CHV_OK;
+}
+
+// ---- chv_scale_lanczos_rgb_ladder: every rendition of every 4-component plane in one launch per route ----
+// Pictures per descriptor slot: a picture's n_rungs target planes and its source plane (stored once) must fit one slot together.
+// include/chipvideo.h states the rule as CHV_RGB_LADDER_CHUNK.
+static constexpr int lanczos_rgb_ladder_chunk(int n_rungs) { return (int)(kDescSlotBytes / (((size_t)n_rungs + 1) * sizeof(DPlane))); }
+static_assert(CHV_RGB_LADDER_CHUNK(1) == 124 && CHV_RGB_LADDER_CHUNK(8) == 27 &&
+              lanczos_rgb_ladder_chunk(1) == CHV_RGB_LADDER_CHUNK(1) && lanczos_rgb_ladder_chunk(4) == CHV_RGB_LADDER_CHUNK(4) &&
+              lanczos_rgb_ladder_chunk(CHV_LADDER_MAX_RUNGS) == CHV_RGB_LADDER_CHUNK(CHV_LADDER_MAX_RUNGS) && lanczos_rgb_ladder_chunk(CHV_LADDER_MAX_RUNGS) >= 1,
+              "a chunk is what fits one descriptor slot (include/chipvideo.h states the rule)");
+
+extern "C" int chv_scale_lanczos_rgb_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
+    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
+    if (n_rungs == 0 || n == 0) return CHV_OK;
+    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    const LanczosRgbLadderLauncher launcher = g_lanczos_rgb_ladder_launcher.load(std::memory_order_acquire);
+    // a picture's record: the target plane of rung 0, of rung 1, ..., then the source plane
+    const size_t per = (size_t)n_rungs + 1, src_at = (size_t)n_rungs;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        for (int r = 0; r < n_rungs; r++) {
+            const chv_image &d = dsts[(size_t)r * n + i];
+            if (d.n_planes != 1) return fail(CHV_ERR_BAD_TARGET, "Lanczos RGB ladder: rung %d, target %d must be one 4-component plane", r, i);
+            int rc = plane_to_device(d.planes[0], 4, c->device, &pi[r], CHV_ERR_BAD_TARGET, "target", r * n + i);
+            if (rc) return rc;
+            if (pi[r].w != planes[r].w || pi[r].h != planes[r].h)
+                return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, pi[r].w, pi[r].h,
+                            planes[r].w, planes[r].h);
+        }
+        if (srcs[i].n_planes != 1) return fail(CHV_ERR_BAD_INPUT, "Lanczos RGB ladder: source %d must be one 4-component plane", i);
+        int rc = plane_to_device(srcs[i].planes[0], 4, c->device, &pi[src_at], CHV_ERR_BAD_INPUT, "input", i);
+        if (rc) return rc;
+        if (pi[src_at].w != planes[src_at].w || pi[src_at].h != planes[src_at].h)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, pi[src_at].w, pi[src_at].h,
+                        planes[src_at].w, planes[src_at].h);
+    }
+    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos RGB ladder kernels");
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    int rc = wait_for_uploads(c->stream, dp);
+    if (rc) return rc;
+    // two tables per rung, from the shared cache; every reference is held until the last launch is enqueued, so a ladder that brings more
+    // geometries than the cache has room for cannot lose a table it has already collected
+    LanczosRef refs[2 * CHV_LADDER_MAX_RUNGS];
+    LanczosRgbLadderJob job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs;
+    job.src_w = planes[src_at].w; job.src_h = planes[src_at].h;
+    for (int r = 0; r < n_rungs; r++) {
+        LanczosRgbLadderRung &R = job.rung[r];
+        R.w = planes[r].w; R.h = planes[r].h;
+        LanczosRef &rx = refs[2 * r], &ry = refs[2 * r + 1];
+        rc = lanczos_table(c, job.src_w, R.w, &rx);
+        if (rc) return rc;
+        rc = lanczos_table(c, job.src_h, R.h, &ry);
+        if (rc) return rc;
+        R.tab = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
+    }
+    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES, so
+    // all rungs of a picture leave in one chunk
+    const int per_slot = lanczos_rgb_ladder_chunk(n_rungs);
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        job.batch = dev; job.n_pictures = m;
+        (void)hipGetLastError();
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_rgb_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        if (e != hipSuccess) return hip_fail(e, "lanczos RGB ladder launch");
     }
     return CHV_OK;
 }

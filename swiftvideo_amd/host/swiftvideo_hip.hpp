@@ -619,6 +619,24 @@ inline ComputeContext scaleLanczosFromYuv(ComputeContext ctx, const std::vector<
     return ctx;
 }
 
+// The ladder of 4-component planes (chv_scale_lanczos_rgb_ladder): rungs[r][i] receives what scaleLanczos(ctx,
+// rungs[r][i], srcs[i]) would write for BGRA or RGBA pictures — every rendition of every source in one launch per route (the wave-per-strip
+// rungs in one, the tile rungs in at most one more).  Up to CHV_LADDER_MAX_RUNGS rungs, each with one target per source; one size per rung,
+// one source size; bytes keep their component order.
+inline ComputeContext scaleLanczosRgbLadder(ComputeContext ctx, const std::vector<std::vector<PictureSample>> &rungs, const std::vector<PictureSample> &srcs) {
+    const size_t n = srcs.size();
+    std::vector<chv_image> d(rungs.size() * n), s(n);
+    for (size_t i = 0; i < n; i++)
+        if (!describe(srcs[i], &s[i])) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    for (size_t r = 0; r < rungs.size(); r++) {
+        if (rungs[r].size() != n) throw ComputeError(CHV_ERR_INVALID_VALUE, "a rung has one target per source");
+        for (size_t i = 0; i < n; i++)
+            if (!describe(rungs[r][i], &d[r * n + i])) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    }
+    check(chv_scale_lanczos_rgb_ladder(ctx.get(), d.data(), (int)rungs.size(), s.data(), (int)n));
+    return ctx;
+}
+
 // Lanczos-3 between the two 4:2:0 packings (chv_scale_lanczos_420): an nv12 or y420p picture into an nv12 or y420p
 // picture, any of the four pairs — the logical planes Y, Cb and Cr resampled one by one as scaleLanczos resamples a 1-component plane and
 // stored in the target's packing; at equal sizes an exact repack.  A same-format pair writes what scaleLanczos writes.

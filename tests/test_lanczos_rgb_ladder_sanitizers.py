@@ -1,0 +1,59 @@
+"""The host path of chv_scale_lanczos_rgb_ladder (swiftvideo_amd/csrc/chipvideo.cpp: validation of every rung of every picture,
+dependencies, the two tables of every rung from the shared cache — up to 16 references — held until the last launch is enqueued, the
+descriptor ring across chunk boundaries with records of n_rungs target planes + the source plane, the launch counter) compiled for the CPU
+against the stand-in HIP runtime whose streams execute LAZILY (tests/stubhip/), with a stand-in launcher that reads the ends of every table
+and touches every plane's ends of every rung when the stream gets to it, and driven by tests/stubhip/lanczos_rgb_ladder_stress.cpp — a
+stand-alone program — under AddressSanitizer + UBSan and under ThreadSanitizer: every refusal, lists longer than a chunk, fresh geometries
+churning the table cache, an injected launch failure on the second of two launches, several threads with a context each while two more free
+and re-create pictures, and the build without a launcher."""
+import os
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+STUB = ROOT / "tests" / "stubhip"
+OUT = STUB / "_build"
+CSRC = ROOT / "swiftvideo_amd" / "csrc"
+
+
+def _build(kind):
+    OUT.mkdir(exist_ok=True)
+    exe = OUT / f"lanczos_rgb_ladder_stress_{kind}"
+    srcs = [CSRC / "chipvideo.cpp", CSRC / "geom_store.cpp", CSRC / "lanczos_from_yuv.h", CSRC / "lanczos_from_yuv_ladder.h", CSRC / "lanczos_rgb_ladder.h", CSRC / "lanczos_420.h", CSRC / "lanczos_planar_ladder.h",
+            CSRC / "lanczos_ladder.h", CSRC / "lanczos_to_yuv.h", CSRC / "lanczos_planar.h", CSRC / "rebind.h", CSRC / "device_types.h", CSRC / "geom_cache.h",
+            CSRC / "switches.h", ROOT / "include" / "chipvideo.h", STUB / "stub_runtime.cpp", STUB / "stub_launchers.cpp",
+            STUB / "stub_lanczos_rgb_ladder_launcher.cpp", STUB / "lanczos_rgb_ladder_stress.cpp", STUB / "hip" / "hip_runtime.h", STUB / "build_lanczos_rgb_ladder.sh"]
+    if not exe.exists() or exe.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
+        subprocess.check_call(["bash", str(STUB / "build_lanczos_rgb_ladder.sh"), kind, str(exe)])
+    return exe
+
+
+def _env():
+    env = dict(os.environ, STUBHIP_DEVICES="2", ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
+               TSAN_OPTIONS="halt_on_error=0:second_deadlock_stack=1")
+    for k in list(env):
+        if k.startswith("CHV_"):
+            del env[k]
+    return env
+
+
+@pytest.mark.parametrize("kind", ["address", "thread"])
+def test_lanczos_rgb_ladder_host_logic_under_sanitizers(kind):
+    exe = _build(kind)
+    out = subprocess.run([str(exe), "6"], capture_output=True, text=True, env=_env(), timeout=900)
+    text = out.stdout + out.stderr
+    assert out.returncode == 0 and "lanczos_rgb_ladder_stress: ok" in text, text[-4000:]
+    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
+
+
+def test_without_a_launcher_the_entry_is_not_implemented():
+    """the host units as tests/stubhip/build.sh links them — no unit that defines the launcher: chipvideo.cpp reaches it through a pointer it
+    owns, null meaning CHV_ERR_NOT_IMPLEMENTED, after validation"""
+    text = (CSRC / "chipvideo.cpp").read_text()
+    assert "register_lanczos_rgb_ladder_launcher" in text and "launch_lanczos_rgb_ladder" not in text
+    assert "lanczos_rgb" not in (STUB / "build.sh").read_text()
+    exe = _build("none")
+    out = subprocess.run([str(exe), "unregistered"], capture_output=True, text=True, env=_env(), timeout=300)
+    assert out.returncode == 0 and "not implemented without a launcher, ok" in out.stdout, (out.stdout + out.stderr)[-4000:]
