@@ -2219,12 +2219,77 @@ static int lanczos_table(chv_context *c, int in_size, int out_size, LanczosRef *
     return CHV_OK;
 }
 
+// ---- the common host path of the Lanczos entries ----
+// Pictures per descriptor slot: the plane records of one picture — its targets rung by rung, then its source planes once — must fit one
+// slot together, and a chunk is what fits one.  include/chipvideo.h states the same rule per entry (the CHV_*_CHUNK macros and the counts).
+static constexpr int lanczos_chunk(size_t records_per_picture) { return (int)(kDescSlotBytes / (records_per_picture * sizeof(DPlane))); }
+static_assert(CHV_LADDER_SLOT_BYTES == kDescSlotBytes && CHV_LADDER_PLANE_BYTES == sizeof(DPlane), "include/chipvideo.h states the descriptor slot and the plane record");
+
+// The launch prologue, after a call's validation: a build without the entry's launcher refuses (`missing` is that refusal, CHV_OK with a
+// launcher: `launcher ? CHV_OK : fail(...)` keeps the message at the entry), then the device and the uploads the planes wait for.
+static int lanczos_begin(chv_context *c, const DepScope &deps, int missing) {
+    if (missing) return missing;
+    HIP_TRY(hipSetDevice(c->device));
+    auto dp = deps.deps();
+    return wait_for_uploads(c->stream, dp);
+}
+
+// The tables of one plane: (src_w, dst_w), then (src_h, dst_h) — the order the shared cache sees.  The caller owns *rx and *ry and holds
+// them until the last launch of the call is enqueued.
+static int lanczos_table_pair(chv_context *c, int src_w, int src_h, int dst_w, int dst_h, LanczosRef *rx, LanczosRef *ry, LanczosPlaneTables *out) {
+    int rc = lanczos_table(c, src_w, dst_w, rx);
+    if (rc) return rc;
+    rc = lanczos_table(c, src_h, dst_h, ry);
+    if (rc) return rc;
+    *out = LanczosPlaneTables{ (*rx)->first, (*rx)->weights, (*ry)->first, (*ry)->weights, (*rx)->taps, (*ry)->taps };
+    return CHV_OK;
+}
+
+// n pictures of `per` records each leave through the pinned, device-mapped descriptor ring, per_slot pictures to a chunk: a longer list is
+// split along the PICTURES, so all records of a picture leave together.  A DescSlot lives exactly for one chunk's launch; the sticky error
+// is cleared right before launch(dev, m), which sets the job's batch and n_pictures, launches, counts, and returns the entry's status.
+template <class Launch>
+static int lanczos_send(chv_context *c, const DPlane *records, size_t per, int n, int per_slot, Launch launch) {
+    for (int first = 0; first < n; first += per_slot) {
+        const int m = std::min(per_slot, n - first);
+        DescSlot ds(c);
+        if (ds.rc) return ds.rc;
+        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
+        memcpy(host, records + per * first, sizeof(DPlane) * per * (size_t)m);
+        DPlane *dev = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+        (void)hipGetLastError();
+        int rc = launch(dev, m);
+        if (rc) return rc;
+    }
+    return CHV_OK;
+}
+
+// The head of every ladder entry: the list's shape.  *empty: a ladder of no rungs or no sources, which is CHV_OK and does nothing.
+static int lanczos_ladder_header(const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, bool *empty) {
+    *empty = false;
+    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
+    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
+    if (n_rungs == 0 || n == 0) { *empty = true; return CHV_OK; }
+    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    return CHV_OK;
+}
+
+// One target format and one source format per ladder: the list's mistake, not the image's — before anything else of the images is looked at.
+static int lanczos_ladder_formats(const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
+    for (int k = 1; k < n_rungs * n; k++)
+        if (dsts[k].format != dsts[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
+    for (int i = 1; i < n; i++)
+        if (srcs[i].format != srcs[0].format)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    return CHV_OK;
+}
+
 // ---- the 4:2:0 families of chv_scale_lanczos: NV12 (planes of 1 and 2 components) and y420p (three planes of 1), plane by plane ----
-// Pictures per descriptor slot of a batch chunk: a picture's plane pairs must fit one slot together.
-static constexpr int kLanczosChunkNV12 = 62, kLanczosChunkY420P = 41;
-static_assert((size_t)kLanczosChunkNV12 * 2 * 2 * sizeof(DPlane) <= kDescSlotBytes && (size_t)kLanczosChunkY420P * 3 * 2 * sizeof(DPlane) <= kDescSlotBytes,
-              "a chunk's plane pairs must fit one descriptor slot");
-static_assert(kLanczosChunkNV12 <= CHV_LANCZOS_BATCH_CHUNK && kLanczosChunkY420P <= CHV_LANCZOS_BATCH_CHUNK, "no planar chunk is longer than a BGRA one");
+// Pictures per descriptor slot of a batch chunk: a picture's np plane pairs, lanczos_chunk(2 * np).
+static_assert(lanczos_chunk(4) == 62 && lanczos_chunk(6) == 41, "include/chipvideo.h states the counts");
+static_assert(lanczos_chunk(4) <= CHV_LANCZOS_BATCH_CHUNK && lanczos_chunk(6) <= CHV_LANCZOS_BATCH_CHUNK, "no planar chunk is longer than a BGRA one");
 
 // planes of a 4:2:0 Lanczos family, 0 for every other (format, structure)
 static int lanczos_planar_planes(const chv_image *img) {
@@ -2255,12 +2320,8 @@ static int lanczos_planar_job(chv_context *c, const DPlane *pairs, int np, Lancz
     job->n_planes = np;
     for (int p = 0; p < np; p++) {
         const DPlane &d = pairs[2 * p], &s = pairs[2 * p + 1];
-        int rc = lanczos_table(c, s.w, d.w, &refs[2 * p]);
+        int rc = lanczos_table_pair(c, s.w, s.h, d.w, d.h, &refs[2 * p], &refs[2 * p + 1], &job->tab[p]);
         if (rc) return rc;
-        rc = lanczos_table(c, s.h, d.h, &refs[2 * p + 1]);
-        if (rc) return rc;
-        const LanczosTable &tx = *refs[2 * p], &ty = *refs[2 * p + 1];
-        job->tab[p] = LanczosPlaneTables{ tx.first, tx.weights, ty.first, ty.weights, tx.taps, ty.taps };
         job->dst[p] = d; job->src[p] = s;
     }
     return CHV_OK;
@@ -2272,10 +2333,7 @@ static int scale_lanczos_planar(chv_context *c, const chv_image *dst, const chv_
     DepScope deps;
     int rc = lanczos_planar_pairs(c, dst, src, np, 0, pairs);
     if (rc) return rc;
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos kernels"));
     if (rc) return rc;
     LanczosRef refs[2 * kLanczosPlanarMaxPlanes];
     LanczosPlanarJob job;
@@ -2307,31 +2365,18 @@ static int scale_lanczos_planar_batch(chv_context *c, const chv_image *dsts, con
                 return fail(CHV_ERR_INVALID_VALUE, "pair %d, plane %d: %dx%d -> %dx%d, the batch is %dx%d -> %dx%d (one geometry per batch)", i, q / 2,
                             pi[q | 1].w, pi[q | 1].h, pi[q & ~1].w, pi[q & ~1].h, pairs[q | 1].w, pairs[q | 1].h, pairs[q & ~1].w, pairs[q & ~1].h);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    int rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos kernels"));
     if (rc) return rc;
     LanczosRef refs[2 * kLanczosPlanarMaxPlanes];
     LanczosPlanarJob job;
     rc = lanczos_planar_job(c, pairs.data(), np, refs, &job);
     if (rc) return rc;
-    // the plane pairs travel through the descriptor ring, a slot per chunk, like the 4-component batch's
-    const int per_slot = np == 2 ? kLanczosChunkNV12 : kLanczosChunkY420P;
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, pairs.data() + (size_t)2 * np * first, sizeof(DPlane) * 2 * np * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    const size_t per = (size_t)2 * np;
+    return lanczos_send(c, pairs.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         hipError_t e = launcher(job, c->stream);
-        if (e != hipSuccess) return hip_fail(e, "lanczos launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos launch") : CHV_OK;
+    });
 }
 
 extern "C" int chv_scale_lanczos(chv_context *c, const chv_image *dst, const chv_image *src) {
@@ -2349,17 +2394,14 @@ extern "C" int chv_scale_lanczos(chv_context *c, const chv_image *dst, const chv
     if (rc) return rc;
     rc = plane_to_device(src->planes[0], 4, c->device, &s, CHV_ERR_BAD_INPUT, "input", 0);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, CHV_OK);      // (the 4-component kernels are part of every build)
     if (rc) return rc;
     LanczosRef tx, ty;      // held until the launch is enqueued (see LanczosTable)
-    rc = lanczos_table(c, s.w, d.w, &tx);
-    if (rc) return rc;
-    rc = lanczos_table(c, s.h, d.h, &ty);
+    LanczosPlaneTables t;
+    rc = lanczos_table_pair(c, s.w, s.h, d.w, d.h, &tx, &ty, &t);
     if (rc) return rc;
     (void)hipGetLastError();
-    hipError_t e = launch_lanczos(d, s, tx->first, tx->weights, tx->taps, ty->first, ty->weights, ty->taps, c->stream, nullptr, 0, tx->stride, tx->first0, ty->stride);
+    hipError_t e = launch_lanczos(d, s, t.fx, t.wx, t.tx, t.fy, t.wy, t.ty, c->stream, nullptr, 0, tx->stride, tx->first0, ty->stride);
     if (e != hipSuccess) return hip_fail(e, "lanczos launch");
     return CHV_OK;
 }
@@ -2388,39 +2430,23 @@ extern "C" int chv_scale_lanczos_batch(chv_context *c, const chv_image *dsts, co
             return fail(CHV_ERR_INVALID_VALUE, "pair %d: %dx%d -> %dx%d, the batch is %dx%d -> %dx%d (one geometry per batch)", i,
                         pairs[2 * i + 1].w, pairs[2 * i + 1].h, pairs[2 * i].w, pairs[2 * i].h, pairs[1].w, pairs[1].h, pairs[0].w, pairs[0].h);
     }
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    int rc = lanczos_begin(c, deps, CHV_OK);
     if (rc) return rc;
     LanczosRef tx, ty;
-    rc = lanczos_table(c, pairs[1].w, pairs[0].w, &tx);
+    LanczosPlaneTables t;
+    rc = lanczos_table_pair(c, pairs[1].w, pairs[1].h, pairs[0].w, pairs[0].h, &tx, &ty, &t);
     if (rc) return rc;
-    rc = lanczos_table(c, pairs[1].h, pairs[0].h, &ty);
-    if (rc) return rc;
-    // the pairs travel through the pinned, device-mapped descriptor ring (a slot per chunk), like a transient tick's descriptors
-    const int per_slot = CHV_LANCZOS_BATCH_CHUNK;
-    static_assert((size_t)CHV_LANCZOS_BATCH_CHUNK * 2 * sizeof(DPlane) <= kDescSlotBytes, "a chunk's plane pairs must fit one descriptor slot");
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, pairs.data() + 2 * (size_t)first, sizeof(DPlane) * 2 * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
-        (void)hipGetLastError();
-        hipError_t e = launch_lanczos(pairs[0], pairs[1], tx->first, tx->weights, tx->taps, ty->first, ty->weights, ty->taps, c->stream, dev, m, tx->stride, tx->first0, ty->stride);
-        if (e != hipSuccess) return hip_fail(e, "lanczos launch");
-    }
-    return CHV_OK;
+    // (the ABI's chunk of 64 pairs is shorter than what a slot holds)
+    static_assert(CHV_LANCZOS_BATCH_CHUNK <= lanczos_chunk(2), "a chunk's plane pairs must fit one descriptor slot");
+    return lanczos_send(c, pairs.data(), 2, n, CHV_LANCZOS_BATCH_CHUNK, [&](DPlane *dev, int m) {
+        hipError_t e = launch_lanczos(pairs[0], pairs[1], t.fx, t.wx, t.tx, t.fy, t.wy, t.ty, c->stream, dev, m, tx->stride, tx->first0, ty->stride);
+        return e != hipSuccess ? hip_fail(e, "lanczos launch") : CHV_OK;
+    });
 }
 
 // ---- chv_scale_lanczos_to_yuv: one BGRA / RGBA plane -> an NV12 or y420p picture ----
-// Pictures per descriptor slot of a batch chunk: a picture's target planes and its source plane must fit one slot together.
-static constexpr int kLanczosToYuvChunkNV12 = 83, kLanczosToYuvChunkY420P = 62;
-static_assert((size_t)kLanczosToYuvChunkNV12 * 3 * sizeof(DPlane) <= kDescSlotBytes && (size_t)(kLanczosToYuvChunkNV12 + 1) * 3 * sizeof(DPlane) > kDescSlotBytes &&
-              (size_t)kLanczosToYuvChunkY420P * 4 * sizeof(DPlane) <= kDescSlotBytes && (size_t)(kLanczosToYuvChunkY420P + 1) * 4 * sizeof(DPlane) > kDescSlotBytes,
-              "a chunk is what fits one descriptor slot (include/chipvideo.h states the counts)");
+// Pictures per descriptor slot of a batch chunk: a picture's np target planes and its source plane, lanczos_chunk(np + 1).
+static_assert(lanczos_chunk(3) == 83 && lanczos_chunk(4) == 62, "a chunk is what fits one descriptor slot (include/chipvideo.h states the counts)");
 
 // DESIGN.md section 4.5's table (the device's copy is kR2Y, pixel_math.hip.h): yoff, then the y, u and v rows over (R, G, B)
 static const int32_t kR2YHost[4][10] = {
@@ -2456,10 +2482,9 @@ static void lanczos_to_yuv_matrix(int src_format, const chv_kernel_opts *opts, i
     kv[r] = k[7]; kv[1] = k[8]; kv[b] = k[9];
 }
 
-static void lanczos_to_yuv_job(const DPlane *planes, int np, int src_format, const chv_kernel_opts *opts, const LanczosTable &tx, const LanczosTable &ty,
-                               LanczosToYuvJob *job) {
+static void lanczos_to_yuv_job(const DPlane *planes, int np, int src_format, const chv_kernel_opts *opts, const LanczosPlaneTables &t, LanczosToYuvJob *job) {
     memset(job, 0, sizeof *job);
-    job->fx = tx.first; job->wx = tx.weights; job->fy = ty.first; job->wy = ty.weights; job->tx = tx.taps; job->ty = ty.taps;
+    job->fx = t.fx; job->wx = t.wx; job->fy = t.fy; job->wy = t.wy; job->tx = t.tx; job->ty = t.ty;
     job->n_dst = np;
     for (int p = 0; p < np; p++) job->dst[p] = planes[p];
     job->src = planes[np];
@@ -2474,19 +2499,15 @@ extern "C" int chv_scale_lanczos_to_yuv(chv_context *c, const chv_image *dst, co
     DepScope deps;
     int rc = lanczos_to_yuv_planes(c, dst, src, 0, planes);
     if (rc) return rc;
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos to YUV kernels");
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos to YUV kernels"));
+    if (rc) return rc;
     const int np = dst->n_planes;
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    rc = wait_for_uploads(c->stream, dp);
-    if (rc) return rc;
     LanczosRef tx, ty;      // held until the launch is enqueued (see LanczosTable)
-    rc = lanczos_table(c, planes[np].w, planes[0].w, &tx);
-    if (rc) return rc;
-    rc = lanczos_table(c, planes[np].h, planes[0].h, &ty);
+    LanczosPlaneTables t;
+    rc = lanczos_table_pair(c, planes[np].w, planes[np].h, planes[0].w, planes[0].h, &tx, &ty, &t);
     if (rc) return rc;
     LanczosToYuvJob job;
-    lanczos_to_yuv_job(planes, np, src->format, opts, *tx, *ty, &job);
+    lanczos_to_yuv_job(planes, np, src->format, opts, t, &job);
     job.batch = nullptr; job.n_pictures = 1;
     (void)hipGetLastError();
     hipError_t e = launcher(job, c->stream);
@@ -2520,64 +2541,40 @@ extern "C" int chv_scale_lanczos_to_yuv_batch(chv_context *c, const chv_image *d
             return fail(CHV_ERR_INVALID_VALUE, "pair %d: %dx%d -> %dx%d, the batch is %dx%d -> %dx%d (one geometry per batch)", i,
                         pi[np].w, pi[np].h, pi[0].w, pi[0].h, planes[np].w, planes[np].h, planes[0].w, planes[0].h);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos to YUV kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    int rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos to YUV kernels"));
     if (rc) return rc;
     LanczosRef tx, ty;
-    rc = lanczos_table(c, planes[np].w, planes[0].w, &tx);
-    if (rc) return rc;
-    rc = lanczos_table(c, planes[np].h, planes[0].h, &ty);
+    LanczosPlaneTables t;
+    rc = lanczos_table_pair(c, planes[np].w, planes[np].h, planes[0].w, planes[0].h, &tx, &ty, &t);
     if (rc) return rc;
     LanczosToYuvJob job;
-    lanczos_to_yuv_job(planes.data(), np, srcs[0].format, opts, *tx, *ty, &job);
-    // the planes travel through the pinned, device-mapped descriptor ring (a slot per chunk), like chv_scale_lanczos_batch's pairs
-    const int per_slot = np == 2 ? kLanczosToYuvChunkNV12 : kLanczosToYuvChunkY420P;
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    lanczos_to_yuv_job(planes.data(), np, srcs[0].format, opts, t, &job);
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         hipError_t e = launcher(job, c->stream);
-        if (e != hipSuccess) return hip_fail(e, "lanczos launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos launch") : CHV_OK;
+    });
 }
 
 // ---- chv_scale_lanczos_to_yuv_ladder: every rung of an encoder ladder in one launch per route ----
-// Pictures per descriptor slot of a chunk: a picture's target planes of every rung and its source plane — stored once — must fit one slot
-// together.  include/chipvideo.h states the rule as CHV_LADDER_CHUNK.
-static_assert(CHV_LADDER_SLOT_BYTES == kDescSlotBytes && CHV_LADDER_PLANE_BYTES == sizeof(DPlane), "include/chipvideo.h states the descriptor slot and the plane record");
+// Pictures per descriptor slot of a chunk: a picture's np target planes of every rung and its source plane, lanczos_chunk(n_rungs * np + 1).
+// include/chipvideo.h states the rule as CHV_LADDER_CHUNK.
 static_assert(CHV_LADDER_MAX_RUNGS == kLanczosLadderMaxRungs, "lanczos_ladder.h carries as many rungs as the ABI admits");
-static constexpr int lanczos_ladder_chunk(int n_rungs, int np) { return (int)(kDescSlotBytes / ((size_t)(n_rungs * np + 1) * sizeof(DPlane))); }
-static_assert(lanczos_ladder_chunk(1, 2) == kLanczosToYuvChunkNV12 && lanczos_ladder_chunk(1, 3) == kLanczosToYuvChunkY420P,
-              "a ladder of one rung is chunked like chv_scale_lanczos_to_yuv_batch");
-static_assert(lanczos_ladder_chunk(CHV_LADDER_MAX_RUNGS, 3) >= 1 && lanczos_ladder_chunk(2, 2) == CHV_LADDER_CHUNK(2, 2) && lanczos_ladder_chunk(8, 3) == CHV_LADDER_CHUNK(8, 3),
+static_assert(CHV_LADDER_CHUNK(1, 2) == lanczos_chunk(3) && CHV_LADDER_CHUNK(1, 3) == lanczos_chunk(4), "a ladder of one rung is chunked like chv_scale_lanczos_to_yuv_batch");
+static_assert(lanczos_chunk(CHV_LADDER_MAX_RUNGS * 3 + 1) >= 1 && lanczos_chunk(2 * 2 + 1) == CHV_LADDER_CHUNK(2, 2) && lanczos_chunk(8 * 3 + 1) == CHV_LADDER_CHUNK(8, 3),
               "the longest ladder of the widest format fits one descriptor slot; a chunk is what fits one (include/chipvideo.h states the rule)");
 
 extern "C" int chv_scale_lanczos_to_yuv_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, const chv_kernel_opts *opts) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
-    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
-    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
-    if (n_rungs == 0 || n == 0) return CHV_OK;
-    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
     const LanczosLadderLauncher launcher = g_lanczos_ladder_launcher.load(std::memory_order_acquire);
     const int np = lanczos_planar_planes(&dsts[0]);
     if (!np) return fail(CHV_ERR_BAD_TARGET, "Lanczos to YUV: target 0 must be nv12 with 2 planes or y420p with 3");
-    // (one target format and one source format per ladder: the list's mistake, not the image's — before anything else is looked at)
-    for (int k = 1; k < n_rungs * n; k++)
-        if (dsts[k].format != dsts[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
-    for (int i = 1; i < n; i++)
-        if (srcs[i].format != srcs[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    rc = lanczos_ladder_formats(dsts, n_rungs, srcs, n);
+    if (rc) return rc;
     // a picture's descriptor: the np target planes of rung 0, of rung 1, ..., then the source plane
     const size_t per = (size_t)n_rungs * np + 1;
     std::vector<DPlane> planes(per * n);
@@ -2586,7 +2583,7 @@ extern "C" int chv_scale_lanczos_to_yuv_ladder(chv_context *c, const chv_image *
         DPlane *pi = planes.data() + per * i;
         for (int r = 0; r < n_rungs; r++) {
             DPlane one[kLanczosToYuvMaxPlanes + 1];
-            int rc = lanczos_to_yuv_planes(c, &dsts[(size_t)r * n + i], &srcs[i], r * n + i, one);
+            rc = lanczos_to_yuv_planes(c, &dsts[(size_t)r * n + i], &srcs[i], r * n + i, one);
             if (rc) return rc;
             for (int p = 0; p < np; p++) pi[r * np + p] = one[p];
             pi[per - 1] = one[np];
@@ -2598,12 +2595,9 @@ extern "C" int chv_scale_lanczos_to_yuv_ladder(chv_context *c, const chv_image *
             return fail(CHV_ERR_INVALID_VALUE, "source %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, pi[per - 1].w, pi[per - 1].h,
                         planes[per - 1].w, planes[per - 1].h);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos ladder kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos ladder kernels"));
     if (rc) return rc;
-    // two tables per rung, from the shared cache (rungs of one geometry share theirs); held until the last launch is enqueued
+    // two tables per rung (rungs of one geometry share theirs)
     LanczosRef refs[2 * CHV_LADDER_MAX_RUNGS];
     LanczosLadderJob job;
     memset(&job, 0, sizeof job);
@@ -2611,63 +2605,41 @@ extern "C" int chv_scale_lanczos_to_yuv_ladder(chv_context *c, const chv_image *
     job.src_w = planes[per - 1].w; job.src_h = planes[per - 1].h;
     for (int r = 0; r < n_rungs; r++) {
         const DPlane &d = planes[r * np];
-        rc = lanczos_table(c, job.src_w, d.w, &refs[2 * r]);
+        LanczosPlaneTables t;
+        rc = lanczos_table_pair(c, job.src_w, job.src_h, d.w, d.h, &refs[2 * r], &refs[2 * r + 1], &t);
         if (rc) return rc;
-        rc = lanczos_table(c, job.src_h, d.h, &refs[2 * r + 1]);
-        if (rc) return rc;
-        const LanczosTable &tx = *refs[2 * r], &ty = *refs[2 * r + 1];
-        job.rung[r] = LanczosLadderRung{ tx.first, tx.weights, ty.first, ty.weights, tx.taps, ty.taps, d.w, d.h };
+        job.rung[r] = LanczosLadderRung{ t.fx, t.wx, t.fy, t.wy, t.tx, t.ty, d.w, d.h };
     }
     lanczos_to_yuv_matrix(srcs[0].format, opts, &job.yoff, job.ky, job.ku, job.kv);
-    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES, so
-    // all rungs of a picture leave in one chunk
-    const int per_slot = lanczos_ladder_chunk(n_rungs, np);
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         int launches = 0;
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
-        if (e != hipSuccess) return hip_fail(e, "lanczos ladder launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos ladder launch") : CHV_OK;
+    });
 }
 
 // ---- chv_scale_lanczos_ladder: every rung of a 4:2:0 ladder in one launch per route ----
-// Pictures per descriptor slot of a chunk: a picture's target planes of every rung and its source planes — stored once — must fit one slot
-// together.  include/chipvideo.h states the rule as CHV_PLANAR_LADDER_CHUNK.
+// Pictures per descriptor slot of a chunk: a picture's np target planes of every rung and its np source planes, lanczos_chunk((n_rungs + 1) * np).
+// include/chipvideo.h states the rule as CHV_PLANAR_LADDER_CHUNK.
 static_assert(CHV_LADDER_MAX_RUNGS == kLanczosPlanarLadderMaxRungs, "lanczos_planar_ladder.h carries as many rungs as the ABI admits");
-static constexpr int lanczos_planar_ladder_chunk(int n_rungs, int np) { return (int)(kDescSlotBytes / ((size_t)(n_rungs + 1) * np * sizeof(DPlane))); }
-static_assert(lanczos_planar_ladder_chunk(1, 2) == kLanczosChunkNV12 && lanczos_planar_ladder_chunk(1, 3) == kLanczosChunkY420P,
-              "a ladder of one rung is chunked like chv_scale_lanczos_batch");
-static_assert(lanczos_planar_ladder_chunk(CHV_LADDER_MAX_RUNGS, 3) >= 1 && lanczos_planar_ladder_chunk(2, 2) == CHV_PLANAR_LADDER_CHUNK(2, 2) &&
-              lanczos_planar_ladder_chunk(3, 3) == CHV_PLANAR_LADDER_CHUNK(3, 3) && lanczos_planar_ladder_chunk(8, 3) == CHV_PLANAR_LADDER_CHUNK(8, 3),
+static_assert(CHV_PLANAR_LADDER_CHUNK(1, 2) == lanczos_chunk(4) && CHV_PLANAR_LADDER_CHUNK(1, 3) == lanczos_chunk(6), "a ladder of one rung is chunked like chv_scale_lanczos_batch");
+static_assert(lanczos_chunk((CHV_LADDER_MAX_RUNGS + 1) * 3) >= 1 && lanczos_chunk((2 + 1) * 2) == CHV_PLANAR_LADDER_CHUNK(2, 2) &&
+              lanczos_chunk((3 + 1) * 3) == CHV_PLANAR_LADDER_CHUNK(3, 3) && lanczos_chunk((8 + 1) * 3) == CHV_PLANAR_LADDER_CHUNK(8, 3),
               "the longest ladder of the widest format fits one descriptor slot; a chunk is what fits one (include/chipvideo.h states the rule)");
 
 extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
-    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
-    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
-    if (n_rungs == 0 || n == 0) return CHV_OK;
-    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
     const LanczosPlanarLadderLauncher launcher = g_lanczos_planar_ladder_launcher.load(std::memory_order_acquire);
     const int np = lanczos_planar_planes(&dsts[0]);
     if (!np) return fail(CHV_ERR_BAD_TARGET, "Lanczos ladder: target 0 must be nv12 with 2 planes or y420p with 3 (there is no 4-component ladder)");
-    // (one format per list: the list's mistake, not the image's — before anything else is looked at)
-    for (int k = 1; k < n_rungs * n; k++)
-        if (dsts[k].format != dsts[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
-    for (int i = 1; i < n; i++)
-        if (srcs[i].format != srcs[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    rc = lanczos_ladder_formats(dsts, n_rungs, srcs, n);
+    if (rc) return rc;
     // a picture's record: the np target planes of rung 0, of rung 1, ..., then the np source planes
     const size_t per = (size_t)(n_rungs + 1) * np, src_at = (size_t)n_rungs * np;
     std::vector<DPlane> planes(per * n);
@@ -2676,7 +2648,7 @@ extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, i
         DPlane *pi = planes.data() + per * i;
         for (int r = 0; r < n_rungs; r++) {
             DPlane pairs[2 * kLanczosPlanarMaxPlanes];
-            int rc = lanczos_planar_pairs(c, &dsts[(size_t)r * n + i], &srcs[i], np, r * n + i, pairs);
+            rc = lanczos_planar_pairs(c, &dsts[(size_t)r * n + i], &srcs[i], np, r * n + i, pairs);
             if (rc) return rc;
             for (int p = 0; p < np; p++) {
                 pi[r * np + p] = pairs[2 * p];
@@ -2692,13 +2664,9 @@ extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, i
                 return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
                             pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos ladder kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos ladder kernels"));
     if (rc) return rc;
-    // two tables per plane per rung, from the shared cache (planes of one geometry share theirs); every reference is held until the last
-    // launch is enqueued, so a ladder that brings more geometries than the cache has room for cannot lose a table it has already collected
+    // two tables per plane per rung (planes of one geometry share theirs)
     LanczosRef refs[2 * kLanczosPlanarMaxPlanes * CHV_LADDER_MAX_RUNGS];
     LanczosPlanarLadderJob job;
     memset(&job, 0, sizeof job);
@@ -2707,40 +2675,25 @@ extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, i
     for (int r = 0; r < n_rungs; r++) {
         for (int p = 0; p < np; p++) {
             const DPlane &d = planes[r * np + p];
-            LanczosRef &rx = refs[2 * (r * kLanczosPlanarMaxPlanes + p)], &ry = refs[2 * (r * kLanczosPlanarMaxPlanes + p) + 1];
-            rc = lanczos_table(c, job.src_w[p], d.w, &rx);
+            LanczosRef *rp = &refs[2 * (r * kLanczosPlanarMaxPlanes + p)];
+            rc = lanczos_table_pair(c, job.src_w[p], job.src_h[p], d.w, d.h, &rp[0], &rp[1], &job.rung[r].tab[p]);
             if (rc) return rc;
-            rc = lanczos_table(c, job.src_h[p], d.h, &ry);
-            if (rc) return rc;
-            job.rung[r].tab[p] = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
             job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
         }
     }
-    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES, so
-    // all rungs of a picture leave in one chunk
-    const int per_slot = lanczos_planar_ladder_chunk(n_rungs, np);
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         int launches = 0;
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_planar_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
-        if (e != hipSuccess) return hip_fail(e, "lanczos planar ladder launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos planar ladder launch") : CHV_OK;
+    });
 }
 
 // ---- chv_scale_lanczos_420 / chv_scale_lanczos_420_ladder: Lanczos-3 between NV12 and y420p ----
-static constexpr int lanczos_420_chunk(int n_rungs, int dnp, int snp) { return (int)(kDescSlotBytes / (((size_t)n_rungs * dnp + snp) * sizeof(DPlane))); }
-static_assert(lanczos_420_chunk(3, 2, 3) == CHV_420_LADDER_CHUNK(3, 2, 3) && lanczos_420_chunk(8, 3, 2) == CHV_420_LADDER_CHUNK(8, 3, 2) &&
-              lanczos_420_chunk(8, 3, 2) >= 1 && lanczos_420_chunk(4, 3, 3) == lanczos_planar_ladder_chunk(4, 3) &&
+// Pictures per descriptor slot of a chunk: a picture's dnp target planes of every rung and its snp source planes, lanczos_chunk(n_rungs * dnp + snp).
+static_assert(lanczos_chunk(3 * 2 + 3) == CHV_420_LADDER_CHUNK(3, 2, 3) && lanczos_chunk(8 * 3 + 2) == CHV_420_LADDER_CHUNK(8, 3, 2) &&
+              lanczos_chunk(8 * 3 + 2) >= 1 && CHV_420_LADDER_CHUNK(4, 3, 3) == CHV_PLANAR_LADDER_CHUNK(4, 3) &&
               CHV_420_LADDER_CHUNK(5, 2, 2) == CHV_PLANAR_LADDER_CHUNK(5, 2),
               "a chunk is what fits one descriptor slot (include/chipvideo.h states the rule); same-format lists are chunked like chv_scale_lanczos_ladder");
 
@@ -2762,38 +2715,31 @@ static int lanczos_420_planes(chv_context *c, const chv_image *img, int err, con
 extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
-    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
-    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
-    if (n_rungs == 0 || n == 0) return CHV_OK;
-    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
     const Lanczos420Launcher launcher = g_lanczos_420_launcher.load(std::memory_order_acquire);
     const int dnp = lanczos_planar_planes(&dsts[0]), snp = lanczos_planar_planes(&srcs[0]);
     if (!dnp) return fail(CHV_ERR_BAD_TARGET, "Lanczos 4:2:0: target 0 must be nv12 with 2 planes or y420p with 3");
     if (!snp) return fail(CHV_ERR_BAD_INPUT, "Lanczos 4:2:0: source 0 must be nv12 with 2 planes or y420p with 3");
-    // (one format per list: the list's mistake, not the image's — before anything else is looked at)
-    for (int k = 1; k < n_rungs * n; k++)
-        if (dsts[k].format != dsts[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
-    for (int i = 1; i < n; i++)
-        if (srcs[i].format != srcs[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    rc = lanczos_ladder_formats(dsts, n_rungs, srcs, n);
+    if (rc) return rc;
     // a picture's record: the dnp target planes of rung 0, of rung 1, ..., then the snp source planes
     const size_t per = (size_t)n_rungs * dnp + snp, src_at = (size_t)n_rungs * dnp;
     std::vector<DPlane> planes(per * n);
     DepScope deps;
     for (int i = 0; i < n; i++) {
         DPlane *pi = planes.data() + per * i;
+        int np = 0;
         for (int r = 0; r < n_rungs; r++) {
-            int np = 0;
-            int rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
+            rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
             if (rc) return rc;
             for (int p = 0; p < dnp; p++)
                 if (pi[r * dnp + p].w != planes[r * dnp + p].w || pi[r * dnp + p].h != planes[r * dnp + p].h)
                     return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p,
                                 pi[r * dnp + p].w, pi[r * dnp + p].h, planes[r * dnp + p].w, planes[r * dnp + p].h);
         }
-        int np = 0;
-        int rc = lanczos_420_planes(c, &srcs[i], CHV_ERR_BAD_INPUT, "input", i, pi + src_at, &np);
+        rc = lanczos_420_planes(c, &srcs[i], CHV_ERR_BAD_INPUT, "input", i, pi + src_at, &np);
         if (rc) return rc;
         for (int p = 0; p < snp; p++)
             if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
@@ -2802,12 +2748,9 @@ extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dst
     }
     // same-format lists are chv_scale_lanczos_ladder's: its launchers, its counter, its bytes
     if (dnp == snp) return chv_scale_lanczos_ladder(c, dsts, n_rungs, srcs, n);
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no 4:2:0 conversion Lanczos kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no 4:2:0 conversion Lanczos kernels"));
     if (rc) return rc;
-    // two tables per logical plane per rung, from the shared cache; every reference is held until the last launch is enqueued
+    // two tables per logical plane per rung
     LanczosRef refs[2 * kLanczosPlanarMaxPlanes * CHV_LADDER_MAX_RUNGS];
     Lanczos420Job job;
     memset(&job, 0, sizeof job);
@@ -2817,33 +2760,19 @@ extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dst
     for (int r = 0; r < n_rungs; r++) {
         for (int p = 0; p < dnp; p++) {
             const DPlane &d = planes[r * dnp + p];
-            LanczosRef &rx = refs[2 * (r * kLanczosPlanarMaxPlanes + p)], &ry = refs[2 * (r * kLanczosPlanarMaxPlanes + p) + 1];
-            rc = lanczos_table(c, p ? job.chroma_w : job.luma_w, d.w, &rx);
+            LanczosRef *rp = &refs[2 * (r * kLanczosPlanarMaxPlanes + p)];
+            rc = lanczos_table_pair(c, p ? job.chroma_w : job.luma_w, p ? job.chroma_h : job.luma_h, d.w, d.h, &rp[0], &rp[1], &job.rung[r].tab[p]);
             if (rc) return rc;
-            rc = lanczos_table(c, p ? job.chroma_h : job.luma_h, d.h, &ry);
-            if (rc) return rc;
-            job.rung[r].tab[p] = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
             job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
         }
     }
-    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES
-    const int per_slot = lanczos_420_chunk(n_rungs, dnp, snp);
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         int launches = 0;
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_420_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
-        if (e != hipSuccess) return hip_fail(e, "lanczos 4:2:0 ladder launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos 4:2:0 ladder launch") : CHV_OK;
+    });
 }
 
 extern "C" int chv_scale_lanczos_420(chv_context *c, const chv_image *dst, const chv_image *src) {
@@ -2860,10 +2789,9 @@ extern "C" int chv_scale_lanczos_420(chv_context *c, const chv_image *dst, const
 }
 
 // ---- chv_scale_lanczos_from_yuv: an NV12 or y420p picture -> one BGRA / RGBA plane ----
-// Pictures per descriptor slot of a batch chunk: a picture's target plane and its source planes must fit one slot together — the counts of
+// Pictures per descriptor slot of a batch chunk: a picture's target plane and its np source planes, lanczos_chunk(1 + np) — the counts of
 // chv_scale_lanczos_to_yuv_batch, whose pictures have as many plane records.
-static constexpr int kLanczosFromYuvChunkNV12 = kLanczosToYuvChunkNV12, kLanczosFromYuvChunkY420P = kLanczosToYuvChunkY420P;
-static_assert(kLanczosFromYuvChunkNV12 == 83 && kLanczosFromYuvChunkY420P == 62, "include/chipvideo.h states the counts");
+static_assert(lanczos_chunk(1 + 2) == 83 && lanczos_chunk(1 + 3) == 62, "include/chipvideo.h states the counts");
 
 // DESIGN.md section 4.2's table (the device's copy is kCsc, pixel_math.hip.h): yoff, cy, crv, cgu, cgv, cbu
 static const int32_t kY2RHost[4][6] = {
@@ -2891,25 +2819,27 @@ static int lanczos_from_yuv_planes(chv_context *c, const chv_image *dst, const c
     return CHV_OK;
 }
 
+// section 4.2's row for `opts` (NULL: BT.601 limited) into a LanczosFromYuvJob or a LanczosFromYuvLadderJob
+template <class Job>
+static void lanczos_from_yuv_matrix(const chv_kernel_opts *opts, Job *job) {
+    const int32_t *k = kY2RHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
+    job->yoff = k[0]; job->cy = k[1]; job->crv = k[2]; job->cgu = k[3]; job->cgv = k[4]; job->cbu = k[5];
+}
+
 // the four tables of one geometry (held in refs until the launch is enqueued) and everything else of the job but the batch
 static int lanczos_from_yuv_job(chv_context *c, const DPlane *planes, int np, int dst_format, const chv_kernel_opts *opts, LanczosRef *refs,
                                 LanczosFromYuvJob *job) {
     memset(job, 0, sizeof *job);
     for (int p = 0; p < 2; p++) {
         const DPlane &s = planes[1 + p];
-        int rc = lanczos_table(c, s.w, planes[0].w, &refs[2 * p]);
+        int rc = lanczos_table_pair(c, s.w, s.h, planes[0].w, planes[0].h, &refs[2 * p], &refs[2 * p + 1], p ? &job->chroma : &job->luma);
         if (rc) return rc;
-        rc = lanczos_table(c, s.h, planes[0].h, &refs[2 * p + 1]);
-        if (rc) return rc;
-        const LanczosTable &tx = *refs[2 * p], &ty = *refs[2 * p + 1];
-        (p ? job->chroma : job->luma) = LanczosPlaneTables{ tx.first, tx.weights, ty.first, ty.weights, tx.taps, ty.taps };
     }
     job->dst = planes[0];
     for (int p = 0; p < np; p++) job->src[p] = planes[1 + p];
     job->src_planes = np;
     job->rgba = dst_format == CHV_FMT_RGBA;
-    const int32_t *k = kY2RHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
-    job->yoff = k[0]; job->cy = k[1]; job->crv = k[2]; job->cgu = k[3]; job->cgv = k[4]; job->cbu = k[5];
+    lanczos_from_yuv_matrix(opts, job);
     return CHV_OK;
 }
 
@@ -2922,10 +2852,7 @@ extern "C" int chv_scale_lanczos_from_yuv(chv_context *c, const chv_image *dst, 
     int np = 0;
     int rc = lanczos_from_yuv_planes(c, dst, src, 0, planes, &np);
     if (rc) return rc;
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV kernels"));
     if (rc) return rc;
     LanczosRef refs[4];      // held until the launch is enqueued (see LanczosTable)
     LanczosFromYuvJob job;
@@ -2971,59 +2898,39 @@ extern "C" int chv_scale_lanczos_from_yuv_batch(chv_context *c, const chv_image 
                         pi[1].w, pi[1].h, pi[0].w, pi[0].h, first[1].w, first[1].h, first[0].w, first[0].h);
         std::copy(pi, pi + per, planes.begin() + per * i);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV kernels"));
     if (rc) return rc;
     LanczosRef refs[4];
     LanczosFromYuvJob job;
     rc = lanczos_from_yuv_job(c, planes.data(), np, dsts[0].format, opts, refs, &job);
     if (rc) return rc;
-    // the planes travel through the pinned, device-mapped descriptor ring (a slot per chunk), like chv_scale_lanczos_to_yuv_batch's
-    const int per_slot = np == 2 ? kLanczosFromYuvChunkNV12 : kLanczosFromYuvChunkY420P;
-    for (int at = 0; at < n; at += per_slot) {
-        const int m = std::min(per_slot, n - at);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * at, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         hipError_t e = launcher(job, c->stream);
         if (e != hipSuccess) return hip_fail(e, "lanczos from YUV launch");
-        debug_counters().lanczos_from_yuv_launches.fetch_add(1, std::memory_order_relaxed);
-    }
-    return CHV_OK;
+        debug_counters().lanczos_from_yuv_launches.fetch_add(1, std::memory_order_relaxed);      // (only launches that were made)
+        return (int)CHV_OK;
+    });
 }
 
 // ---- chv_scale_lanczos_from_yuv_ladder: every BGRA / RGBA rendition of every decoded picture in one launch per route ----
-// Pictures per descriptor slot: a picture's n_rungs target planes and its source planes (stored once) must fit one slot together.
+// Pictures per descriptor slot: a picture's n_rungs target planes and its snp source planes, lanczos_chunk(n_rungs + snp).
 // include/chipvideo.h states the rule as CHV_FROM_YUV_LADDER_CHUNK; with one rung it gives the batch's counts.
-static constexpr int lanczos_from_yuv_ladder_chunk(int n_rungs, int snp) { return (int)(kDescSlotBytes / (((size_t)n_rungs + snp) * sizeof(DPlane))); }
-static_assert(lanczos_from_yuv_ladder_chunk(1, 2) == kLanczosFromYuvChunkNV12 && lanczos_from_yuv_ladder_chunk(1, 3) == kLanczosFromYuvChunkY420P &&
+static_assert(CHV_FROM_YUV_LADDER_CHUNK(1, 2) == lanczos_chunk(1 + 2) && CHV_FROM_YUV_LADDER_CHUNK(1, 3) == lanczos_chunk(1 + 3) &&
               CHV_FROM_YUV_LADDER_CHUNK(1, 2) == 83 && CHV_FROM_YUV_LADDER_CHUNK(1, 3) == 62 &&
-              lanczos_from_yuv_ladder_chunk(8, 2) == CHV_FROM_YUV_LADDER_CHUNK(8, 2) && lanczos_from_yuv_ladder_chunk(8, 3) == CHV_FROM_YUV_LADDER_CHUNK(8, 3) &&
-              lanczos_from_yuv_ladder_chunk(CHV_LADDER_MAX_RUNGS, 3) >= 1,
+              lanczos_chunk(8 + 2) == CHV_FROM_YUV_LADDER_CHUNK(8, 2) && lanczos_chunk(8 + 3) == CHV_FROM_YUV_LADDER_CHUNK(8, 3) &&
+              lanczos_chunk(CHV_LADDER_MAX_RUNGS + 3) >= 1,
               "a chunk is what fits one descriptor slot (include/chipvideo.h states the rule); one rung is chunked like chv_scale_lanczos_from_yuv_batch");
 
 extern "C" int chv_scale_lanczos_from_yuv_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n, const chv_kernel_opts *opts) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
-    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
-    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
-    if (n_rungs == 0 || n == 0) return CHV_OK;
-    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
     const LanczosFromYuvLadderLauncher launcher = g_lanczos_from_yuv_ladder_launcher.load(std::memory_order_acquire);
-    // (one format per list: the list's mistake, not the image's — before anything else is looked at)
-    for (int k = 1; k < n_rungs * n; k++)
-        if (dsts[k].format != dsts[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d has format %d, the ladder began with %d (one target format per ladder)", k / n, k % n, dsts[k].format, dsts[0].format);
-    for (int i = 1; i < n; i++)
-        if (srcs[i].format != srcs[0].format)
-            return fail(CHV_ERR_INVALID_VALUE, "source %d has format %d, the ladder began with %d (one source format per ladder)", i, srcs[i].format, srcs[0].format);
+    rc = lanczos_ladder_formats(dsts, n_rungs, srcs, n);
+    if (rc) return rc;
     // a picture's record: the target plane of rung 0, of rung 1, ..., then the snp source planes
     const int snp0 = lanczos_planar_planes(&srcs[0]);
     const int snp = snp0 ? snp0 : 2;                   // (a source that is neither packing is refused below, by its own status)
@@ -3035,7 +2942,7 @@ extern "C" int chv_scale_lanczos_from_yuv_ladder(chv_context *c, const chv_image
         for (int r = 0; r < n_rungs; r++) {
             DPlane one[1 + kLanczosPlanarMaxPlanes];
             int np = 0;
-            int rc = lanczos_from_yuv_planes(c, &dsts[(size_t)r * n + i], &srcs[i], r * n + i, one, &np);
+            rc = lanczos_from_yuv_planes(c, &dsts[(size_t)r * n + i], &srcs[i], r * n + i, one, &np);
             if (rc) return rc;
             if (np != snp) return fail(CHV_ERR_INVALID_VALUE, "source %d has %d planes, the ladder began with %d (one source format per ladder)", i, np, snp);
             pi[r] = one[0];
@@ -3048,12 +2955,9 @@ extern "C" int chv_scale_lanczos_from_yuv_ladder(chv_context *c, const chv_image
             return fail(CHV_ERR_INVALID_VALUE, "source %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, pi[src_at].w, pi[src_at].h,
                         planes[src_at].w, planes[src_at].h);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV ladder kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos from YUV ladder kernels"));
     if (rc) return rc;
-    // four tables per rung, from the shared cache; every reference is held until the last launch is enqueued
+    // four tables per rung
     LanczosRef refs[4 * CHV_LADDER_MAX_RUNGS];
     LanczosFromYuvLadderJob job;
     memset(&job, 0, sizeof job);
@@ -3061,56 +2965,39 @@ extern "C" int chv_scale_lanczos_from_yuv_ladder(chv_context *c, const chv_image
     job.rgba = dsts[0].format == CHV_FMT_RGBA;
     job.luma_w = planes[src_at].w; job.luma_h = planes[src_at].h;
     job.chroma_w = planes[src_at + 1].w; job.chroma_h = planes[src_at + 1].h;
-    const int32_t *k = kY2RHost[(opts ? opts->colorspace : CHV_CSC_BT601_LIMITED) & 3];
-    job.yoff = k[0]; job.cy = k[1]; job.crv = k[2]; job.cgu = k[3]; job.cgv = k[4]; job.cbu = k[5];
+    lanczos_from_yuv_matrix(opts, &job);
     for (int r = 0; r < n_rungs; r++) {
         LanczosFromYuvLadderRung &R = job.rung[r];
         R.w = planes[r].w; R.h = planes[r].h;
         for (int p = 0; p < 2; p++) {
-            LanczosRef &rx = refs[4 * r + 2 * p], &ry = refs[4 * r + 2 * p + 1];
-            rc = lanczos_table(c, p ? job.chroma_w : job.luma_w, R.w, &rx);
+            LanczosRef *rp = &refs[4 * r + 2 * p];
+            rc = lanczos_table_pair(c, p ? job.chroma_w : job.luma_w, p ? job.chroma_h : job.luma_h, R.w, R.h, &rp[0], &rp[1], p ? &R.chroma : &R.luma);
             if (rc) return rc;
-            rc = lanczos_table(c, p ? job.chroma_h : job.luma_h, R.h, &ry);
-            if (rc) return rc;
-            (p ? R.chroma : R.luma) = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
         }
     }
-    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES
-    const int per_slot = lanczos_from_yuv_ladder_chunk(n_rungs, snp);
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         int launches = 0;
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_from_yuv_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
-        if (e != hipSuccess) return hip_fail(e, "lanczos from YUV ladder launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos from YUV ladder launch") : CHV_OK;
+    });
 }
 
 // ---- chv_scale_lanczos_rgb_ladder: every rendition of every 4-component plane in one launch per route ----
-// Pictures per descriptor slot: a picture's n_rungs target planes and its source plane (stored once) must fit one slot together.
+// Pictures per descriptor slot: a picture's n_rungs target planes and its source plane, lanczos_chunk(n_rungs + 1).
 // include/chipvideo.h states the rule as CHV_RGB_LADDER_CHUNK.
-static constexpr int lanczos_rgb_ladder_chunk(int n_rungs) { return (int)(kDescSlotBytes / (((size_t)n_rungs + 1) * sizeof(DPlane))); }
 static_assert(CHV_RGB_LADDER_CHUNK(1) == 124 && CHV_RGB_LADDER_CHUNK(8) == 27 &&
-              lanczos_rgb_ladder_chunk(1) == CHV_RGB_LADDER_CHUNK(1) && lanczos_rgb_ladder_chunk(4) == CHV_RGB_LADDER_CHUNK(4) &&
-              lanczos_rgb_ladder_chunk(CHV_LADDER_MAX_RUNGS) == CHV_RGB_LADDER_CHUNK(CHV_LADDER_MAX_RUNGS) && lanczos_rgb_ladder_chunk(CHV_LADDER_MAX_RUNGS) >= 1,
+              lanczos_chunk(1 + 1) == CHV_RGB_LADDER_CHUNK(1) && lanczos_chunk(4 + 1) == CHV_RGB_LADDER_CHUNK(4) &&
+              lanczos_chunk(CHV_LADDER_MAX_RUNGS + 1) == CHV_RGB_LADDER_CHUNK(CHV_LADDER_MAX_RUNGS) && lanczos_chunk(CHV_LADDER_MAX_RUNGS + 1) >= 1,
               "a chunk is what fits one descriptor slot (include/chipvideo.h states the rule)");
 
 extern "C" int chv_scale_lanczos_rgb_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
-    if (n_rungs < 0 || n_rungs > CHV_LADDER_MAX_RUNGS) return fail(CHV_ERR_INVALID_VALUE, "a ladder has 0 to %d rungs, not %d", CHV_LADDER_MAX_RUNGS, n_rungs);
-    if (n < 0) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: %d sources", n);
-    if (n_rungs == 0 || n == 0) return CHV_OK;
-    if (!dsts || !srcs) return fail(CHV_ERR_INVALID_VALUE, "bad ladder: a null list");
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
     const LanczosRgbLadderLauncher launcher = g_lanczos_rgb_ladder_launcher.load(std::memory_order_acquire);
     // a picture's record: the target plane of rung 0, of rung 1, ..., then the source plane
     const size_t per = (size_t)n_rungs + 1, src_at = (size_t)n_rungs;
@@ -3121,26 +3008,22 @@ extern "C" int chv_scale_lanczos_rgb_ladder(chv_context *c, const chv_image *dst
         for (int r = 0; r < n_rungs; r++) {
             const chv_image &d = dsts[(size_t)r * n + i];
             if (d.n_planes != 1) return fail(CHV_ERR_BAD_TARGET, "Lanczos RGB ladder: rung %d, target %d must be one 4-component plane", r, i);
-            int rc = plane_to_device(d.planes[0], 4, c->device, &pi[r], CHV_ERR_BAD_TARGET, "target", r * n + i);
+            rc = plane_to_device(d.planes[0], 4, c->device, &pi[r], CHV_ERR_BAD_TARGET, "target", r * n + i);
             if (rc) return rc;
             if (pi[r].w != planes[r].w || pi[r].h != planes[r].h)
                 return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, pi[r].w, pi[r].h,
                             planes[r].w, planes[r].h);
         }
         if (srcs[i].n_planes != 1) return fail(CHV_ERR_BAD_INPUT, "Lanczos RGB ladder: source %d must be one 4-component plane", i);
-        int rc = plane_to_device(srcs[i].planes[0], 4, c->device, &pi[src_at], CHV_ERR_BAD_INPUT, "input", i);
+        rc = plane_to_device(srcs[i].planes[0], 4, c->device, &pi[src_at], CHV_ERR_BAD_INPUT, "input", i);
         if (rc) return rc;
         if (pi[src_at].w != planes[src_at].w || pi[src_at].h != planes[src_at].h)
             return fail(CHV_ERR_INVALID_VALUE, "source %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, pi[src_at].w, pi[src_at].h,
                         planes[src_at].w, planes[src_at].h);
     }
-    if (!launcher) return fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos RGB ladder kernels");
-    HIP_TRY(hipSetDevice(c->device));
-    auto dp = deps.deps();
-    int rc = wait_for_uploads(c->stream, dp);
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no Lanczos RGB ladder kernels"));
     if (rc) return rc;
-    // two tables per rung, from the shared cache; every reference is held until the last launch is enqueued, so a ladder that brings more
-    // geometries than the cache has room for cannot lose a table it has already collected
+    // two tables per rung
     LanczosRef refs[2 * CHV_LADDER_MAX_RUNGS];
     LanczosRgbLadderJob job;
     memset(&job, 0, sizeof job);
@@ -3149,32 +3032,16 @@ extern "C" int chv_scale_lanczos_rgb_ladder(chv_context *c, const chv_image *dst
     for (int r = 0; r < n_rungs; r++) {
         LanczosRgbLadderRung &R = job.rung[r];
         R.w = planes[r].w; R.h = planes[r].h;
-        LanczosRef &rx = refs[2 * r], &ry = refs[2 * r + 1];
-        rc = lanczos_table(c, job.src_w, R.w, &rx);
+        rc = lanczos_table_pair(c, job.src_w, job.src_h, R.w, R.h, &refs[2 * r], &refs[2 * r + 1], &R.tab);
         if (rc) return rc;
-        rc = lanczos_table(c, job.src_h, R.h, &ry);
-        if (rc) return rc;
-        R.tab = LanczosPlaneTables{ rx->first, rx->weights, ry->first, ry->weights, rx->taps, ry->taps };
     }
-    // the planes travel through the pinned, device-mapped descriptor ring, a slot per chunk; a longer list is split along the PICTURES, so
-    // all rungs of a picture leave in one chunk
-    const int per_slot = lanczos_rgb_ladder_chunk(n_rungs);
-    for (int first = 0; first < n; first += per_slot) {
-        const int m = std::min(per_slot, n - first);
-        DescSlot ds(c);
-        if (ds.rc) return ds.rc;
-        DPlane *host = (DPlane *)(c->desc_host + (size_t)ds.slot * kDescSlotBytes);
-        memcpy(host, planes.data() + per * first, sizeof(DPlane) * per * (size_t)m);
-        DPlane *dev = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void **)&dev, host, 0));
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
-        (void)hipGetLastError();
         int launches = 0;
         hipError_t e = launcher(job, c->stream, &launches);
         debug_counters().lanczos_rgb_ladder_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
-        if (e != hipSuccess) return hip_fail(e, "lanczos RGB ladder launch");
-    }
-    return CHV_OK;
+        return e != hipSuccess ? hip_fail(e, "lanczos RGB ladder launch") : CHV_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------

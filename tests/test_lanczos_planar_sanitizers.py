@@ -21,9 +21,9 @@ def _build(kind):
     exe = OUT / f"lanczos_planar_stress_{kind}"
     srcs = [CSRC / "chipvideo.cpp", CSRC / "geom_store.cpp", CSRC / "lanczos_planar.h", CSRC / "rebind.h", CSRC / "device_types.h", CSRC / "geom_cache.h",
             CSRC / "switches.h", ROOT / "include" / "chipvideo.h", STUB / "stub_runtime.cpp", STUB / "stub_launchers.cpp",
-            STUB / "stub_lanczos_planar_launcher.cpp", STUB / "lanczos_planar_stress.cpp", STUB / "hip" / "hip_runtime.h", STUB / "build_lanczos_planar.sh"]
+            STUB / "stub_lanczos_planar_launcher.cpp", STUB / "lanczos_planar_stress.cpp", STUB / "hip" / "hip_runtime.h", STUB / "build_lanczos.sh"]
     if not exe.exists() or exe.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-        subprocess.check_call(["bash", str(STUB / "build_lanczos_planar.sh"), kind, str(exe)])
+        subprocess.check_call(["bash", str(STUB / "build_lanczos.sh"), "planar", kind, str(exe)])
     return exe
 
 
