@@ -1,5 +1,5 @@
-"""An independent float64 statement of the compositing kernels of DESIGN.md sections 4.1, 4.2, 4.3 and 4.5, and the rounding bound of their
-specified f32 chains.
+"""An independent float64 statement of the compositing kernels of DESIGN.md sections 4.1, 4.2, 4.3 and 4.5 and of the reference's own kernels
+on 4:2:0 canvases, and the rounding bound of their specified f32 chains.
 
 Written from DESIGN.md section 4, the reference's OpenCL kernel family and the OpenCL 1.2 text (section 8.2: LINEAR / CLAMP_TO_EDGE /
 normalized coordinates; section 8.3.1.1: UNORM_INT8 is c / 255 on the way in and sat(rte(255 f)) on the way out) — over whole planes, with
@@ -23,6 +23,16 @@ the plane; the chroma planes of a 4:2:0 source are sampled at the same uv with t
       float rgb2yuv rows, cur (1 - af) + f af clamped to [0, 1] (luma) / [-1, 1] (chroma) on the unit scale.  Stored: sat(rte(255 .)).
   4:2:0 canvas, the four `_int` kernels (4.5): the structure of 4.1 on the code scale with F = R2Y(rte(255 fill)) for the fill and
       P = R2Y(rte(sample R, G, B)) for the picture, a = sample_A opacity / 255.
+  4:2:0 canvas, float RGB source (the reference's img_{bgra,rgba}_{nv12,y420p}; family "premul": colours are multiplied by their alpha BEFORE
+      the matrix and blended with the same alpha after it).  On the unit scale, with M the float rgb2yuv rows and off their fourth column:
+      NOTHING is written unless the pixel is inside the border quad AND tx is inside — the fill is never painted between the two.  There
+          alpha = opacity fill.a        F_k = M_k . (fill.r alpha, fill.g alpha, fill.b alpha, 1) = alpha sum_c M_kc fill_c + off_k
+          r_k = cur_k / 255 (1 - alpha) + F_k alpha          chroma clamped to [-1, 1], luma NOT clamped
+      and where uv is inside as well, with s the unit-scale sample (img_bgra_*: bytes 0 and 2 exchanged, the kernel's .zyxw — the picture is
+      read in memory order R, G, B, A):
+          a2 = s_A opacity              P_k = M_k . (s_R a2, s_G a2, s_B a2, 1)              r_k = r_k (1 - a2) + P_k a2        (no clamp)
+      so the offset 0.5 of the chroma rows rides through both blends: r = r0 (1 - a2) + a2^2 sum_c M_kc s_c + off a2.  Luma at every pixel,
+      chroma from the quad's even/even pixel if the target plane has that sample.  Stored: sat(rte(255 .)).
   Metal img_bgra_bgra: the texel at trunc(x inW / outW), c a + dst (1 - a) with a = c_A / 255, alpha 255, over the whole canvas.
 After each layer the canvas is the stored codes (4.3).
 
@@ -46,6 +56,16 @@ THE BOUND, derived from the chain DESIGN.md specifies, never fitted.  u = 2^-24,
   Blend and fill, unit scale.  cur / 255, 1 - alpha, two products, the sum, . 255 at the store: gamma(5) . 255 on top of the sample's
   bound; the fill's alpha = opacity fill.a (one rounding) and its colour (a dot product with the rgb2yuv rows, carried as above) enter by
   their own bounds.  Metal: c / 255 three times, 1 - a, two products, a sum, . 255: gamma(6) . 255.
+  Float RGB source on a 4:2:0 canvas ("premul").  The chain is linear in each colour sample, quadratic in a2 and non-decreasing in the canvas
+  value, so no corner of the SAMPLE is taken: the whole chain is carried as (value, e) pairs through the product and sum rules of "Geometry"
+  above, which ARE the mean-value bound  |dr| <= a2^2 sum_c |M_kc| e_c + e_a (|r0| + 2 a2 |S| + |off| + e_a |S|) + roundings  term by term
+  (|a| eb + |b| ea + ea eb per product: the second-order term included), and the canvas interval is taken at its two ends.  Counted, one u
+  each unless exempt as above: the sample gamma(7) (c / 255, two for the weight, the product, three sums — and it is NOT exempt where the
+  weights are exact, c / 255 still rounds) plus its position term; a2 = s_A opacity; s_c a2; per row three products by M (off . 1 is exact)
+  and three sums in ((x + y) + z) + w order; 1 - a2; r (1 - a2); P a2; their sum; . 255 at the store.  The longest path, a colour sample to
+  the stored byte, carries 7 + 1 + 1 + 1 + 3 + 1 + 1 + 1 = 16 roundings.  The fill: alpha; fill_c alpha; the same row; cur / 255; 1 - alpha;
+  two products; the sum — 4 from the canvas and 8 from a fill component to r0, which then goes through the picture's blend (3) and the store.
+  The clamp is 1-Lipschitz and carries the bound unchanged.
   Everything gets 1e-9 for this module's own float64 arithmetic.
 
 OUTCOME: per byte an interval [lo, hi] of codes.  A value within its bound of a rounding tie gives two codes; the integer matrices are
@@ -56,8 +76,7 @@ truncation likewise; the interval of one layer is the canvas of the next.
 CAPS (conditions on a case, counted from this module alone before any output is looked at): per case at most 5 % of the compared bytes with
 lo != hi and at most 3 % with hi - lo > 4; pooled over a test module 2.5 % and 1 %; a case under 400 compared bytes counts in the pool only.
 
-SCOPE: opacity and fill components in [0, 1]; source planes at most 512 wide.  The float RGB -> YUV kernels img_{bgra,rgba}_{nv12,y420p}
-are not stated here: their premultiplied chain is not monotone in the sample."""
+SCOPE: opacity and fill components in [0, 1]; source planes at most 512 wide."""
 import itertools
 
 import numpy as np
@@ -76,6 +95,8 @@ KERNELS = {"img_nv12_bgra": ("nv12", "bgra", "code"), "img_y420p_bgra": ("y420p"
            "img_nv12_nv12": ("nv12", "nv12", "unit"), "img_y420p_nv12": ("y420p", "nv12", "unit"), "img_y420p_y420p": ("y420p", "y420p", "unit"),
            "img_bgra_nv12_int": ("bgra", "nv12", "int"), "img_rgba_nv12_int": ("rgba", "nv12", "int"),
            "img_bgra_y420p_int": ("bgra", "y420p", "int"), "img_rgba_y420p_int": ("rgba", "y420p", "int"),
+           "img_bgra_nv12": ("bgra", "nv12", "premul"), "img_rgba_nv12": ("rgba", "nv12", "premul"),
+           "img_bgra_y420p": ("bgra", "y420p", "premul"), "img_rgba_y420p": ("rgba", "y420p", "premul"),
            "img_bgra_bgra": ("bgra", "bgra", "metal")}
 for _yoff, _y, _u, _v in RGB_TO_YUV.values():
     # the corners r2y_interval takes: Y rises with R, G and B; U falls with R and G and rises with B; V rises with R and falls with G and B
@@ -95,11 +116,15 @@ def blend(p, a, cur):
 
 HOW = dict(out_uv=out_uv,               # (x, size) -> numerator, denominator of out_uv
            blend=blend,
-           swizzle=True,                # RGBA sources: bytes 0 and 2 exchanged
+           swizzle=True,                # RGBA sources: bytes 0 and 2 exchanged (the float RGB -> YUV kernels: BGRA sources, their .zyxw)
            chroma_size=lambda plane_wh, luma_wh: plane_wh,   # the size a chroma plane's uv is scaled by
            alpha_scale=1.0 / 255.0,     # a = sample_A opacity alpha_scale
            chroma_owner=0,              # chroma (i, j) is written from pixel (2 i + owner, 2 j + owner)
-           tap_index=np.floor)
+           tap_index=np.floor,
+           # the float RGB -> YUV kernels ("premul")
+           premul=lambda c, a: _mul(c, a),      # a colour component (value, e) on its way into the matrix: multiplied by its alpha
+           offset_blended=True,         # the matrix offset is part of the blended term: off a, not off
+           fill_inside="tx")            # the fill is painted inside border AND tx only ("border": everywhere inside the border quad, as 4.1)
 
 
 # ---- (value, error) arithmetic of one f32 operation -------------------------------------------------------------------------------------------
@@ -169,16 +194,25 @@ class Geometry:
         border = [_dot(n, m[32 + 4 * i:36 + 4 * i]) for i in range(2)]
         self.uv = [_dot(tx, m[16 + 4 * i:20 + 4 * i]) for i in range(2)]
         self.in_border = _inside(*border)
-        it, iu = _inside(tx[0], tx[1]), _inside(*self.uv)
+        self.in_tx, self.in_uv = it, iu = _inside(tx[0], tx[1]), _inside(*self.uv)
         self.in_picture = (it[0] & iu[0], it[1] & iu[1])
 
     def at(self, sl):
         """the geometry of the pixels sl = (rows, columns) selects"""
         g = object.__new__(Geometry)
         g.uv = [(v[sl], e[sl]) for v, e in self.uv]
-        g.in_border = tuple(m[sl] for m in self.in_border)
-        g.in_picture = tuple(m[sl] for m in self.in_picture)
+        for name in ("in_border", "in_tx", "in_uv", "in_picture"):
+            setattr(g, name, tuple(m[sl] for m in getattr(self, name)))
         return g
+
+    def branches(self, fill_inside="border"):
+        """where each of the three branches may be taken: [untouched, fill only, picture].  "border": the fill everywhere inside the border quad,
+        the picture where tx and uv are inside as well (4.1, 4.5, the YUV-source kernels); "tx": nothing outside border AND tx (premul)"""
+        (b_sure, b_may), (p_sure, p_may) = self.in_border, self.in_picture
+        if fill_inside == "border":
+            return [~b_sure, b_may & ~p_sure, b_may & p_may]
+        assert fill_inside == "tx", fill_inside
+        return [~(b_sure & self.in_tx[0]), b_may & self.in_tx[1] & ~self.in_uv[0], b_may & p_may]
 
 
 # ---- sampling ---------------------------------------------------------------------------------------------------------------------------------
@@ -256,11 +290,10 @@ def _corners(how, p, a, cur):
     return np.minimum.reduce(vals), np.maximum.reduce(vals)
 
 
-def _hull(geo, cur, fill, pic):
+def _hull(geo, cur, fill, pic, fill_inside="border"):
     """the stored interval from the three branches: untouched, fill only, picture (each (lo, hi)); masks broadcast over trailing components"""
-    (b_sure, b_may), (p_sure, p_may) = geo.in_border, geo.in_picture
     pad = (slice(None), slice(None)) + (None,) * (cur[0].ndim - 2)
-    may = [~b_sure[pad], (b_may & ~p_sure)[pad], (b_may & p_may)[pad]]
+    may = [m[pad] for m in geo.branches(fill_inside)]
     lo = np.minimum.reduce([np.where(m, c[0], 1 << 20) for m, c in zip(may, (cur, fill, pic))])
     hi = np.maximum.reduce([np.where(m, c[1], -1) for m, c in zip(may, (cur, fill, pic))])
     return lo, hi
@@ -344,6 +377,16 @@ def _owners(how, W, H, chroma_shape):
     return np.ix_(ys, xs), (slice(0, len(ys)), slice(0, len(xs)))
 
 
+def _premul_blend(how, cur, colour, a, row, clamp):
+    """cur (1 - a) + (row . (colour a, 1)) a as (value, e): one stage of the float RGB -> YUV kernels, for the fill (cur the canvas, a = alpha)
+    and for the picture (cur the fill stage's result, a = a2) alike"""
+    w = 1.0 if how["offset_blended"] else 0.0
+    p = _dot([how["premul"](c, a) for c in colour] + [_val(w)], row)
+    r = _add(_mul(cur, _add(_val(1.0), (-a[0], a[1]))), _mul(p, a))
+    v = how["blend"](p[0], a[0], cur[0]) + (1.0 - w) * row[3]
+    return (np.clip(v, -1.0, 1.0) if clamp else v), r[1]          # the clamp is 1-Lipschitz
+
+
 def _to_420(how, name, W, H, canvas, src, uniforms, csc):
     sfmt, dfmt, family = KERNELS[name]
     u = np.asarray(uniforms, dtype=np.float32).astype(np.float64)
@@ -365,6 +408,24 @@ def _to_420(how, name, W, H, canvas, src, uniforms, csc):
             c0 = cur[k] if k == 0 else tuple(t[own] for t in cur[k])
             out.append(_code_scale(how, g, c0, tuple(t.astype(np.float64) for t in fills[k]), af,
                                    tuple(t.astype(np.float64) for t in p), _alpha(how, s[..., 3], e[..., 3], op)))
+    elif family == "premul":
+        ri, bi = (2, 0) if sfmt == "bgra" and how["swizzle"] else (0, 2)
+        fill = [_val(u[48 + c]) for c in range(3)]
+        for k, g in enumerate(geos):
+            if k < 2:                      # one sample for luma's pixels, one for the chroma owners: both chroma rows share it
+                s, e = sample(src[0], g, how, 7)
+                e = np.where(e == 0.0, gamma(7) * s + OWN, e)         # exact weights: c / 255 rounds all the same
+                picture = [_div_exact((s[..., i], e[..., i]), 255.0) for i in (ri, 1, bi, 3)]
+                a2 = _mul(picture[3], _val(op))
+            c0 = cur[k] if k == 0 else tuple(t[own] for t in cur[k])
+            ends = []
+            for c in c0:                    # the chain is non-decreasing in the canvas value: its interval at its two ends
+                r0 = _premul_blend(how, _div_exact(_val(c), 255.0), fill, af, RGB2YUV_F[k], clamp=k > 0)
+                r = _premul_blend(how, r0, picture[:3], a2, RGB2YUV_F[k], clamp=False)
+                ends.append([_mul(t, _val(255.0)) for t in (r0, r)])
+            eb = [np.maximum(ends[0][i][1], ends[1][i][1]) + OWN for i in range(2)]
+            fl, pic = [(sat_rte(ends[0][i][0] - eb[i]), sat_rte(ends[1][i][0] + eb[i])) for i in range(2)]
+            out.append(_hull(g, c0, fl, pic, how["fill_inside"]))
     else:
         rgb1 = [_val(u[48]), _val(u[49]), _val(u[50]), _val(1.0)]
         eu = 255.0 * gamma(5) + OWN

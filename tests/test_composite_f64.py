@@ -1,4 +1,5 @@
-"""The compositing kernels' restatement against an independent float64 statement (tests/composite_f64.py; DESIGN.md sections 4.1 - 4.3, 4.5).
+"""The compositing kernels' restatement against an independent float64 statement (tests/composite_f64.py; DESIGN.md sections 4.1 - 4.3, 4.5
+and the reference's own kernels on 4:2:0 canvases, the float RGB -> YUV ones included).
 
 Every bit-exact GPU test of the tick kernels builds its expectation from oracle/ref_kernels.c, which was written from the same reading of the
 formulas as the kernels.  Here the oracle is held to the statement's intervals (a) on named cases, each at the smallest size that still has
@@ -18,6 +19,8 @@ from oracle import oracle as O
 BGRA_KERNELS = ["img_nv12_bgra", "img_y420p_bgra", "img_bgra_bgra_tx", "img_rgba_bgra_tx"]
 YUV_KERNELS = {"nv12": ["img_nv12_nv12", "img_y420p_nv12", "img_bgra_nv12_int", "img_rgba_nv12_int"],
                "y420p": ["img_y420p_y420p", "img_bgra_y420p_int", "img_rgba_y420p_int"]}
+# the float RGB -> YUV kernels draw from lists of their own (beside a video layer to lie over), so that the lists above draw what they always drew
+PREMUL_KERNELS = {"nv12": ["img_bgra_nv12", "img_rgba_nv12", "img_nv12_nv12"], "y420p": ["img_bgra_y420p", "img_rgba_y420p", "img_y420p_y420p"]}
 
 
 def L(kernel, iw, ih, seed, csc=0, **kw):
@@ -97,6 +100,29 @@ NAMED = {
                                         L("img_rgba_nv12_int", 16, 10, 67, csc=1, rect=(20.0, 2.0, 15.0, 9.0), opacity=0.4)]),
     "stack-y420p": case("y420p", 52, 34, [L("img_y420p_y420p", 41, 27, 68), L("img_bgra_y420p_int", 20, 14, 69, rect=(5.5, 4.5, 22.0, 15.0)),
                                           L("img_y420p_y420p", 24, 18, 70, rect=(28.3, 15.4, 30.2, 25.1), opacity=0.45)]),
+    # the float RGB -> YUV kernels (the statement's "premul" family), at the sizes of their _int neighbours
+    "up-premul": case("y420p", 30, 18, [L("img_bgra_y420p", 13, 9, 400)], 401),
+    "down-premul": case("nv12", 22, 14, [L("img_rgba_nv12", 61, 47, 402, opacity=0.6519)], 403),
+    "left-top-premul": case("nv12", 40, 26, [L("img_bgra_nv12", 30, 20, 404, rect=(-9.3, -5.7, 31.1, 20.9))], 405),
+    "right-bottom-premul": case("y420p", 40, 26, [L("img_rgba_y420p", 30, 20, 406, rect=(20.6, 12.2, 33.3, 25.1))], 407),
+    "rotated-premul": case("nv12", 48, 30, [L("img_rgba_nv12", 40, 24, 408, rect=(12.0, 7.0, 26.0, 15.0), rotation=2.4)], 409),
+    "border-fill-premul": case("y420p", 44, 28, [L("img_bgra_y420p", 24, 16, 410, rect=(9.3, 6.4, 22.1, 13.3), border=(3.2, 2.3, 4.1, 5.4),
+                                                   fill=(0.2, 0.8, 0.4, 0.35), opacity=0.8137)], 411),
+    "border-fill-premul-nv12": case("nv12", 44, 28, [L("img_rgba_nv12", 24, 16, 412, rect=(9.3, 6.4, 22.1, 13.3), border=(3.2, 2.3, 4.1, 5.4),
+                                                        fill=(0.9, 0.3, 0.55, 0.6), opacity=0.7519)], 413),
+    # a crop reaching outside [0, 1]: pixels inside tx whose uv is outside get the fill alone
+    "crop-outside-premul": case("nv12", 36, 22, [L("img_bgra_nv12", 50, 30, 414, tex=(-0.15, 0.3, 1.2, 0.9), fill=(0.13, 0.27, 0.91, 0.8))], 415),
+    "flip-premul": case("y420p", 36, 22, [L("img_rgba_y420p", 50, 30, 416, tex=(0.9, 0.1, -0.8, 0.8))], 417),
+    "opacity-0-premul": case("nv12", 22, 14, [L("img_bgra_nv12", 14, 11, 418, opacity=0.0, fill=(1.0, 1.0, 1.0, 1.0))], 419),
+    "opacity-1-premul": case("y420p", 22, 14, [L("img_bgra_y420p", 14, 11, 420, opacity=1.0)], 421),
+    "odd-premul-nv12": case("nv12", 27, 15, [L("img_rgba_nv12", 21, 13, 422, rect=(-2.3, 1.2, 30.1, 15.3))], 423),
+    "odd-premul-y420p": case("y420p", 15, 27, [L("img_rgba_y420p", 13, 21, 424, opacity=0.9137)], 425),
+    "2x2-premul": case("nv12", 26, 18, [L("img_bgra_nv12", 2, 2, 426)], 427),
+    # two of them over a video layer on a cleared canvas: per-pixel alpha through re-quantised layers; and a mix on a seeded canvas
+    "stack-premul-video": case("y420p", 52, 34, [L("img_y420p_y420p", 41, 27, 428), L("img_bgra_y420p", 20, 14, 429, rect=(5.5, 4.5, 32.0, 20.0), opacity=0.8137),
+                                                 L("img_rgba_y420p", 24, 18, 430, rect=(18.3, 10.4, 30.2, 21.1), opacity=0.4519)]),
+    "stack-premul-seeded": case("nv12", 52, 34, [L("img_bgra_nv12", 41, 27, 431, opacity=0.7137), L("img_rgba_nv12_int", 20, 14, 432, rect=(5.5, 4.5, 22.0, 15.0)),
+                                                 L("img_rgba_nv12", 24, 18, 433, rect=(20.3, 9.4, 30.2, 22.1), fill=(0.3, 0.6, 0.1, 0.5), border=(2.2, 1.3, 2.1, 1.4))], 434),
 }
 # identity placement on texel centres: a 2^k canvas, a source of the same size moved by half a texel (1 / 2^(k+1) is exact), so that every tap
 # position is an integer and every weight 0 or 1: EVERY byte must be decided, and equal to the source's
@@ -114,12 +140,12 @@ NAMED["aligned-luma-420"] = case("nv12", 16, 8, [L("img_nv12_nv12", 16, 8, 84, t
 
 
 # ---- b. seeded cases in the style of the fuzzers' _random_case -------------------------------------------------------------------------------------
-def random_case(seed):
+def random_case(seed, yuv_kernels=YUV_KERNELS):
     """rectangles across edges, rotation, borders, fill, texture crop and flip, opacity in {0, 1, random}; 1 - 4 layers; every third canvas cleared"""
     rng = np.random.default_rng(seed)
     fmt = ["bgra", "nv12", "bgra", "y420p"][seed % 4]
     W, H = int(rng.integers(8, 150)), int(rng.integers(8, 90))
-    names = BGRA_KERNELS if fmt == "bgra" else YUV_KERNELS[fmt]
+    names = BGRA_KERNELS if fmt == "bgra" else yuv_kernels[fmt]
     layers = []
     for _ in range(int(rng.integers(1, 5))):
         kw = {}
@@ -185,6 +211,30 @@ ROUTES = {
                                           L("img_rgba_nv12_int", 50, 40, 362, rect=(-20.3, -10.2, 120.4, 60.7), opacity=0.35)], 363),
     "yw-y420p-mix": case("y420p", 192, 108, [L("img_y420p_y420p", 192, 108, 370, rect=(-1.2, -0.7, 195.1, 110.3)),
                                              L("img_bgra_y420p_int", 64, 36, 371, csc=1, rect=(8.3, 8.4, 64.2, 36.1), opacity=0.8, fill=(0.2, 0.9, 0.1, 0.45))], 372),
+    # the float RGB -> YUV rows of tick_yuv_stream / tick_yuv_wave, per canvas format: float RGB layers only; a video layer with two of them
+    # over it (the three-layer instantiation of own | RGB kinds); a video, a float RGB and an integer-matrix layer in four (the all-kinds one)
+    **{f"ys-{fmt}-rgb": case(fmt, 256, 96, [L(f"img_bgra_{fmt}", 256, 96, 500 + s, opacity=0.9137, **FR_INT),
+                                            L(f"img_rgba_{fmt}", 64, 36, 501 + s, rect=(30.4, 10.3, 80.1, 45.2), opacity=0.8137)])
+       for fmt, s in (("nv12", 0), ("y420p", 40))},
+    **{f"ys-{fmt}-rgb3": case(fmt, 256, 96, [L(f"img_{fmt}_{fmt}", 384, 144, 510 + s, content="waves", **FR_INT),
+                                             L(f"img_bgra_{fmt}", 96, 54, 511 + s, rect=(100.2, 20.6, 120.3, 70.4), opacity=0.6137, border=(4.2, 4.1, 4.3, 4.4)),
+                                             L(f"img_rgba_{fmt}", 64, 36, 512 + s, rect=(30.4, 10.3, 80.1, 45.2), opacity=0.8137)])
+       for fmt, s in (("nv12", 0), ("y420p", 40))},
+    **{f"ys-{fmt}-all4": case(fmt, 256, 96, [L(f"img_y420p_{fmt}", 384, 144, 520 + s, content="waves", **FR_INT),
+                                             L(f"img_rgba_{fmt}", 64, 36, 521 + s, rect=(30.4, 10.3, 80.1, 45.2), opacity=0.8137),
+                                             L(f"img_bgra_{fmt}_int", 96, 54, 522 + s, csc=1, rect=(100.2, 20.6, 120.3, 70.4), opacity=0.6137),
+                                             L(f"img_bgra_{fmt}", 48, 32, 523 + s, rect=(180.3, 40.2, 70.4, 50.1), opacity=0.7519)])
+       for fmt, s in (("nv12", 0), ("y420p", 40))},
+    # the strip kernel only: border and fill, a flip, a layer across the left and top edges, an uncleared canvas — the edge strips go through the
+    # per-pixel statement of yuv_pixel.hip.h, the interior through the row code
+    "yw-nv12-premul": case("nv12", 260, 70, [L("img_nv12_nv12", 96, 54, 530, rect=(33.3, 9.4, 180.2, 40.1), opacity=0.8137),
+                                             L("img_bgra_nv12", 64, 64, 531, rect=(150.2, 5.3, 90.4, 60.1), tex=(1.0, 0.0, -1.0, 1.0), opacity=0.7137,
+                                               border=(5.2, 3.1, 7.3, 2.4), fill=(0.9, 0.2, 0.1, 0.6)),
+                                             L("img_rgba_nv12", 50, 40, 532, rect=(-20.3, -10.2, 120.4, 60.7), opacity=0.3519)], 533),
+    "yw-y420p-premul": case("y420p", 192, 108, [L("img_rgba_y420p", 192, 108, 570, rect=(-1.2, -0.7, 195.1, 110.3), opacity=0.9137),
+                                                L("img_bgra_y420p", 64, 36, 571, rect=(8.3, 8.4, 64.2, 36.1), opacity=0.8137, fill=(0.2, 0.9, 0.1, 0.45),
+                                                  border=(3.1, 2.2, 4.3, 2.4)),
+                                                L("img_rgba_y420p", 48, 30, 572, rect=(-10.3, -6.2, 80.4, 50.7), tex=(1.0, 0.0, -1.0, 1.0), opacity=0.5519)], 573),
 }
 
 # literal seeds, chosen when the list was written from 100 ... 169 by the statement alone: one whose tick leaves nine tenths of the canvas as it
@@ -193,7 +243,13 @@ ROUTES = {
 SEEDS = [104, 105, 106, 108, 109, 110, 111, 112, 114, 116, 118, 121, 123, 124, 126, 127, 128, 129, 134, 135, 136, 138, 139, 140, 141, 142, 143, 144,
          146, 147, 148, 149, 150, 151, 152, 154, 155, 156, 157, 158, 160, 161, 162, 163, 166, 167, 168, 169]
 SEEDED = {f"seed{s}": random_case(s) for s in SEEDS}
-CASES = {**NAMED, **SEEDED, **ROUTES}
+# the float RGB -> YUV kernels: the same generator drawing from PREMUL_KERNELS.  Literal seeds, chosen the same way from the odd numbers from 201
+# on (s % 4 == 1: NV12, 3: y420p), sixteen of each format: left out were the no-ops and the draws without one of the four kernels; none of
+# these exceeded a cap.  Both conditions are asserted below as well
+SEEDS_PREMUL = [205, 217, 221, 229, 245, 249, 253, 257, 261, 265, 269, 273, 281, 289, 297, 301,
+                203, 215, 219, 223, 235, 243, 247, 251, 255, 263, 267, 271, 275, 279, 283, 287]
+SEEDED_PREMUL = {f"premul-seed{s}": random_case(s, PREMUL_KERNELS) for s in SEEDS_PREMUL}
+CASES = {**NAMED, **SEEDED, **SEEDED_PREMUL, **ROUTES}
 
 
 def waves(noise, seed):
@@ -284,6 +340,9 @@ def test_every_kernel_is_covered_singly_and_in_stacks():
     assert {len(c[4]) for c in CASES.values()} >= {1, 2, 3, 4}
     assert {c[3] is None for c in CASES.values()} == {True, False}
     assert len(SEEDED) >= 40 and all(changed(name) >= 0.10 for name in SEEDED)
+    assert len(SEEDED_PREMUL) >= 24 and all(changed(name) >= 0.10 for name in SEEDED_PREMUL)
+    assert [c[0] for c in SEEDED_PREMUL.values()].count("nv12") == [c[0] for c in SEEDED_PREMUL.values()].count("y420p") == len(SEEDED_PREMUL) // 2
+    assert all(any(F.KERNELS[l[0]][2] == "premul" for l in c[4]) for c in SEEDED_PREMUL.values())
     for fmt, W, H, _, layers in NAMED.values():
         assert 7 <= W <= 150 and 5 <= H <= 90
     for fmt, W, H, _, layers in CASES.values():
@@ -326,11 +385,15 @@ def test_caps_per_case_and_pooled():
 WRONG = {
     "pixel-centred out_uv": (dict(out_uv=lambda x, size: (x + 0.5, size)), ["up-nv12", "down-rgba", "flip-420"]),
     "a and 1 - a exchanged": (dict(blend=lambda p, a, cur: p * (1.0 - a) + cur * a), ["opacity-frac", "opacity-frac-420", "alpha-stack"]),
-    "no RGBA swizzle": (dict(swizzle=False), ["down-rgba", "flip-int"]),
+    "no RGBA swizzle": (dict(swizzle=False), ["down-rgba", "flip-int", "left-top-premul"]),
     "chroma sampled at luma texel coordinates": (dict(chroma_size=lambda plane_wh, luma_wh: luma_wh), ["up-nv12", "down-y420p", "flip-420"]),
     "a = sample_A opacity without / 255": (dict(alpha_scale=1.0), ["up-bgra", "alpha-stack-int"]),
-    "chroma owned by the odd pixel of the quad": (dict(chroma_owner=1), ["flip-420", "up-int", "odd-y420p"]),
+    "chroma owned by the odd pixel of the quad": (dict(chroma_owner=1), ["flip-420", "up-int", "odd-y420p", "up-premul"]),
     "floor replaced by round in the tap index": (dict(tap_index=np.round), ["up-nv12", "up-bgra", "opacity-frac-420"]),
+    # the float RGB -> YUV kernels
+    "colours not multiplied by their alpha before the matrix": (dict(premul=lambda c, a: c), ["up-premul", "border-fill-premul-nv12", "stack-premul-video"]),
+    "the fill painted everywhere inside the border quad": (dict(fill_inside="border"), ["border-fill-premul", "border-fill-premul-nv12"]),
+    "the matrix offset added outside the blend": (dict(offset_blended=False), ["down-premul", "flip-premul"]),
 }
 
 

@@ -26,14 +26,28 @@ PHASED = [f"ph{t}" for t in range(5)]
 BGRA_STRIPS = ["wv-mix", "wv-cover", "wv-metal"]
 YUV_STREAMED = ["ys-nv12-video", "ys-y420p-video", "ys-nv12-int", "ys-y420p-int"]
 YUV_STRIPS = YUV_STREAMED + ["yw-nv12-mix", "yw-y420p-mix"]
+
+
+def float_rgb(name):
+    """the case has a layer of the float RGB -> YUV kernels img_{bgra,rgba}_{nv12,y420p}: those cases have tests of their own below, one test
+    per route and canvas format with the cases in a loop"""
+    return any(F.KERNELS[layer[0]][2] == "premul" for layer in T.CASES[name][4])
+
+
+# the float RGB -> YUV rows: float RGB layers only, a video layer under two of them (own | RGB kinds, three layers), all kinds in four layers
+RGB_STREAMED = {fmt: [f"ys-{fmt}-{tick}" for tick in ("rgb", "rgb3", "all4")] for fmt in ("nv12", "y420p")}
+RGB_STRIP_ONLY = {"nv12": "yw-nv12-premul", "y420p": "yw-y420p-premul"}
 NAMED_BGRA = [n for n, c in T.NAMED.items() if c[0] == "bgra"]
-NAMED_420 = [n for n, c in T.NAMED.items() if c[0] != "bgra"]
+NAMED_420 = [n for n, c in T.NAMED.items() if c[0] != "bgra" and not float_rgb(n)]
+NAMED_RGB_420 = [n for n in T.NAMED if float_rgb(n)]
 ODD_420 = ["odd-nv12", "odd-y420p", "odd-int"]
-SINGLE = {}                # kernel -> the named cases of one layer of it on a seeded canvas
+ODD_RGB_420 = ["odd-premul-nv12", "odd-premul-y420p"]
+SINGLE, SINGLE_RGB = {}, {}                # kernel -> the named cases of one layer of it on a seeded canvas
 for _n, _c in T.NAMED.items():
     if len(_c[4]) == 1 and _c[3] is not None:
-        SINGLE.setdefault(_c[4][0][0], []).append(_n)
-USED = sorted(set(STREAM_LONE + PHASED + BGRA_STRIPS + YUV_STRIPS + list(T.NAMED) + list(T.SEEDED)))
+        (SINGLE_RGB if float_rgb(_n) else SINGLE).setdefault(_c[4][0][0], []).append(_n)
+USED = sorted(set(STREAM_LONE + PHASED + BGRA_STRIPS + YUV_STRIPS + sum(RGB_STREAMED.values(), []) + list(RGB_STRIP_ONLY.values())
+                  + list(T.NAMED) + list(T.SEEDED) + list(T.SEEDED_PREMUL)))
 
 
 def on_device(ctx, name):
@@ -154,6 +168,37 @@ def test_general_yuv(ctx, switch, name):
     batched(ctx, [name], f"tick_general_yuv<{T.CASES[name][0]}>")
 
 
+# ---- 4:2:0 canvases, the float RGB -> YUV kernels: one test per route and canvas format, its cases in a loop -----------------------------------------
+@pytest.mark.parametrize("fmt", ["nv12", "y420p"])
+def test_yuv_stream_float_rgb(ctx, switch, fmt):
+    """tick_yuv_stream's float RGB rows — float RGB layers only, the three-layer own | RGB instantiation, the all-kinds one — batched and lone"""
+    switch("CHV_YUV_STREAM", "force")
+    for name in RGB_STREAMED[fmt]:
+        batched(ctx, [name], f"tick_yuv_stream<{fmt}>")
+        lone(ctx, name, f"tick_yuv_stream<{fmt}>")
+
+
+@pytest.mark.parametrize("fmt", ["nv12", "y420p"])
+def test_yuv_strips_float_rgb(ctx, switch, fmt):
+    """tick_yuv_wave at both strip heights on the same ticks and on the strip-only mix (border and fill, a flip, a layer across the left and top
+    edges, a seeded canvas): the edge strips run the per-pixel statement, the interior the row code"""
+    switch("CHV_YUV_STREAM", "0")
+    for rows in ("8", "16"):
+        switch("CHV_WAVE_ROWS", rows)
+        for name in RGB_STREAMED[fmt] + [RGB_STRIP_ONLY[fmt]]:
+            assert T.CASES[name][0] == fmt
+            batched(ctx, [name], f"tick_yuv_wave<{fmt}>")
+
+
+def test_general_yuv_float_rgb(ctx, switch):
+    """tick_general_yuv: the odd canvases without a switch, then every named case and the strip-only mixes forced onto it"""
+    for name in ODD_RGB_420:
+        batched(ctx, [name], f"tick_general_yuv<{T.CASES[name][0]}>")
+    switch("CHV_FORCE_GENERAL", "1")
+    for name in NAMED_RGB_420 + list(RGB_STRIP_ONLY.values()):
+        batched(ctx, [name], f"tick_general_yuv<{T.CASES[name][0]}>")
+
+
 # ---- the single-kernel entry, the default routes ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kernel", sorted(SINGLE))
 def test_run_compute_kernel_on_a_seeded_canvas(ctx, kernel):
@@ -169,6 +214,24 @@ def test_run_compute_kernel_on_a_seeded_canvas(ctx, kernel):
 def test_seeded_ticks_on_the_route_the_library_chooses(ctx, part):
     """a quarter of the seeded cases per test (every fourth one: all canvas formats in each), one batch per case"""
     for name in list(T.SEEDED)[part::4]:
+        batched(ctx, [name], None)
+
+
+def test_run_compute_kernel_float_rgb_on_a_seeded_canvas(ctx):
+    """every single-layer named case of the four float RGB -> YUV kernels through the single-kernel entry"""
+    assert len(SINGLE_RGB) == 4
+    for kernel in sorted(SINGLE_RGB):
+        for name in SINGLE_RGB[kernel]:
+            target, clear, ((k, src, u, csc),) = on_device(ctx, name)
+            assert not clear and str(k) == kernel
+            sv.usingContext(ctx, lambda c: sv.runComputeKernel(c, images=[src], target=target, kernel=k, uniforms=u, blends=True, colorspace=csc))
+            held(ctx, "runComputeKernel", name, target)
+
+
+@pytest.mark.parametrize("part", range(2))
+def test_seeded_float_rgb_ticks_on_the_route_the_library_chooses(ctx, part):
+    """the seeded cases of the float RGB -> YUV kernels, sixteen per test (every second one: both canvas formats in each), one batch per case"""
+    for name in list(T.SEEDED_PREMUL)[part::2]:
         batched(ctx, [name], None)
 
 
