@@ -75,7 +75,8 @@ int chv_debug_set_switch(const char *name, const char *value);
  * ladder whose rungs all take one route, two for one with rungs on both), and "lanczos_planar_ladder_launches", the same count for
  * chv_scale_lanczos_ladder (process-wide), and "lanczos_420_ladder_launches", the same count for the cross-format path (NV12 -> y420p,
  * y420p -> NV12) of chv_scale_lanczos_420 and chv_scale_lanczos_420_ladder (process-wide; same-format pairs through those entries are forwarded
- * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to), and "lanczos_from_yuv_launches", the device
+ * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to), and "lanczos_to_420_launches", the same count for
+ * the five formats chv_scale_lanczos_to_420 and chv_scale_lanczos_to_420_ladder do not forward (process-wide), and "lanczos_from_yuv_launches", the device
  * launches made by chv_scale_lanczos_from_yuv and chv_scale_lanczos_from_yuv_batch (process-wide: one per call, one per chunk), and
  * "lanczos_from_yuv_ladder_launches", the device launches made by chv_scale_lanczos_from_yuv_ladder (process-wide: one per chunk for a ladder
  * whose rungs all take one route, two for one with rungs on both; that entry does not touch "lanczos_from_yuv_launches"), and
@@ -521,6 +522,42 @@ int chv_scale_lanczos_ladder(chv_context *ctx, const chv_image *dsts, int n_rung
 #define CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) (CHV_LADDER_SLOT_BYTES / (((n_rungs) * (dst_planes) + (src_planes)) * CHV_LADDER_PLANE_BYTES))
 int chv_scale_lanczos_420(chv_context *ctx, const chv_image *dst, const chv_image *src);
 int chv_scale_lanczos_420_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
+/* Lanczos-3 from EVERYTHING the decoder makes into the two 4:2:0 packings: `dst` is an NV12 or y420p picture exactly as
+ * chv_scale_lanczos_420 checks it, `src` a picture of one of
+ *   - CHV_FMT_NV21:                  2 planes (1 and 2 components); Y is plane 0, Cb byte 1 and Cr byte 0 of each texel of plane 1;
+ *   - CHV_FMT_Y422P, CHV_FMT_Y444P:  3 planes of 1 component: Y, Cb, Cr.  The plane sizes the caller gives are taken as they are (a decoder
+ *                                    gives w / 2 x h for 4:2:2 and w x h for 4:4:4); Cb and Cr must agree;
+ *   - CHV_FMT_YUVS (bytes Y0 Cb Y1 Cr) and CHV_FMT_ZVUY (bytes Cb Y0 Cr Y1): 1 plane described with width = the picture's width in pixels,
+ *                                    components = 2 (bytes per pixel), pitch >= 2 x width.  The width must be even; Y is the bytes 0, 2, 4, ...
+ *                                    (yuvs) or 1, 3, 5, ... (zvuy) of a row, Cb the bytes 1, 5, 9, ... or 0, 4, 8, ..., Cr the bytes 3, 7, 11, ... or
+ *                                    2, 6, 10, ...; the chroma images are width / 2 x height.  These are FFmpeg's byte orders for YUYV422 and
+ *                                    UYVY422, because a decoder is where such frames come from; the component lists of
+ *                                    sample.pict.linux.swift:283-286 disagree with them;
+ *   - CHV_FMT_NV12, CHV_FMT_Y420P:   accepted and forwarded to chv_scale_lanczos_420 / chv_scale_lanczos_420_ladder: their bytes, their launchers,
+ *                                    their counters.
+ * Every source has three LOGICAL 1-component images Y, Cb and Cr.  Each is resampled to the size of the same logical image of dst exactly as
+ * chv_scale_lanczos resamples a 1-component plane: its own tables per axis from its own width and height, horizontal then vertical pass, fmaf
+ * per tap from 0 with taps ascending, indices clamped to the image's edge, float intermediate, convert_uchar_sat_rte.  No colour arithmetic, no
+ * re-siting, no cross-plane term.  At equal picture sizes therefore: Y is an exact copy (or unpack); NV21 -> NV12 is an exact byte swap of the
+ * chroma plane and NV21 -> y420p an exact de-interleave; a 4:2:2 source's chroma is untouched horizontally and reduced 2:1 vertically; a 4:4:4
+ * source's chroma is reduced 2:1 on both axes — a 12-tap Lanczos, not a box.
+ * chv_scale_lanczos_to_420_ladder: dsts[r * n + i] is rung r of source i; the call writes the bytes of n_rungs x n single calls.  All sources have
+ * one size and one format, all targets one format, all targets of a rung one size.  All or nothing; n_rungs == 0 or n == 0 is a no-op.
+ * Errors (nothing launched, nothing written):
+ *   - as chv_scale_lanczos_420 for dst                                                                            -> CHV_ERR_BAD_TARGET;
+ *   - a source that is none of the seven formats with the plane and component counts above (BGRA and RGBA are chv_scale_lanczos_to_yuv's), a
+ *     source plane that fails a plane check, Cb and Cr of different size, a packed source of odd width           -> CHV_ERR_BAD_INPUT;
+ *   - differing formats or sizes within a list, a bad count, a NULL list with non-zero counts, n_rungs > CHV_LADDER_MAX_RUNGS, a rung for which
+ *     the 160 KB rule of chv_scale_lanczos refuses ANY logical image (a 4:4:4 source's chroma is reduced twice as hard as its luma, so it can
+ *     be refused where luma passes)                                                                               -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation (forwarded sources still work)                            -> CHV_ERR_NOT_IMPLEMENTED.
+ * Stream order, upload dependencies, a pass's held work and table lifetime as chv_scale_lanczos_batch.  The entries read no switch: a rung
+ * takes the wave-per-strip route when no logical image has more than 22 taps on an axis and no staged row exceeds 64 vectors at its source's
+ * tap stride of 1, 2 or 4 bytes, and the tile route otherwise.  Launches: one per route per chunk, at most two per chunk, counted by
+ * "lanczos_to_420_launches" (chv_debug_get_counter; process-wide; forwarded sources do not touch it).  A chunk is
+ * CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) pictures with src_planes of 1, 2 or 3.  A longer list is split along the PICTURES. */
+int chv_scale_lanczos_to_420(chv_context *ctx, const chv_image *dst, const chv_image *src);
+int chv_scale_lanczos_to_420_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
 /* Lanczos-3 resize of one NV12 or y420p picture INTO a BGRA or RGBA plane of `dst`'s size, in one launch: the decoder side's rendition
  * (DESIGN.md section 4.4.6).  The logical planes Y, Cb and Cr of `src` (NV12: Cb and Cr are components 0 and 1 of plane 1; y420p: planes 1
  * and 2) are each resampled to dst's w x h exactly as chv_scale_lanczos resamples a 1-component plane — the chroma planes straight from

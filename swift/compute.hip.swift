@@ -749,4 +749,80 @@ func scaleLanczos420(_ context: ComputeContext, srcs: [PictureSample], rungs: [[
     try check(chv_scale_lanczos_420_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
     return context
 }
+
+/// The planes of a decoder frame of one of the five formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p), as framePlanes /
+/// planeSize describe them (dec.video.ffmpeg.swift:162-185): plane sizes as there, strides from the frame's linesize array (packed rows when
+/// nil).  A packed 4:2:2 plane is the picture's width x height at two bytes per pixel (yuvs: Y0 Cb Y1 Cr, zvuy: Cb Y0 Cr Y1), which is what
+/// chv_scale_lanczos_to_420 takes.
+func decoderFramePlanes(_ format: PixelFormat, size: Vector2, strides: [Int]? = nil) throws -> [Plane] {
+    let w = Int(size.x), h = Int(size.y)
+    let half = Vector2(Float(w / 2), Float(h / 2)), halfw = Vector2(Float(w / 2), Float(h))
+    var planes: [Plane]
+    switch format {
+    case .nv21:
+        planes = [Plane(size: size, stride: w, bitDepth: 8, components: [.y]),
+                  Plane(size: half, stride: w / 2 * 2, bitDepth: 8, components: [.cr, .cb])]
+    case .yuvs:
+        planes = [Plane(size: size, stride: 2 * w, bitDepth: 8, components: [.y, .cb])]
+    case .zvuy:
+        planes = [Plane(size: size, stride: 2 * w, bitDepth: 8, components: [.cb, .y])]
+    case .y422p:
+        planes = [Plane(size: size, stride: w, bitDepth: 8, components: [.y]),
+                  Plane(size: halfw, stride: w / 2, bitDepth: 8, components: [.cb]),
+                  Plane(size: halfw, stride: w / 2, bitDepth: 8, components: [.cr])]
+    case .y444p:
+        planes = [Plane(size: size, stride: w, bitDepth: 8, components: [.y]),
+                  Plane(size: size, stride: w, bitDepth: 8, components: [.cb]),
+                  Plane(size: size, stride: w, bitDepth: 8, components: [.cr])]
+    default:
+        throw ComputeError.badInputData(description: "Invalid pixel format")
+    }
+    if let strides = strides {
+        guard strides.count >= planes.count else { throw ComputeError.badInputData(description: "one stride per plane") }
+        planes = try zip(planes, strides).map { plane, stride in
+            guard stride >= Int(plane.size.x) * plane.components.count else {
+                throw ComputeError.badInputData(description: "stride shorter than a row")
+            }
+            return Plane(size: plane.size, stride: stride, bitDepth: plane.bitDepth, components: plane.components)
+        }
+    }
+    return planes
+}
+
+/// Lanczos-3 from any of the decoder's seven YUV formats into an nv12 or y420p picture (chv_scale_lanczos_to_420, DESIGN.md section 4.4.9):
+/// nv21, y422p, y444p, yuvs and zvuy sources — nv12 and y420p are forwarded to scaleLanczos420 — with the logical images Y, Cb and Cr
+/// resampled one by one and stored in the target's packing; no colour arithmetic, no re-siting.
+func scaleLanczosTo420(_ context: ComputeContext, src: PictureSample, target: PictureSample) throws -> ComputeContext {
+    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 3) else {
+        throw ComputeError.badTarget
+    }
+    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 3) else {
+        throw ComputeError.badInputData(description: "Bad input image")
+    }
+    try check(chv_scale_lanczos_to_420(context.handle, &targetDesc, &desc))
+    return context
+}
+
+/// The ladder of it (chv_scale_lanczos_to_420_ladder): rungs[r][i] receives what scaleLanczosTo420(context, src: srcs[i], target: rungs[r][i])
+/// would write — one format and one size for all sources, nv12 or y420p for all targets.
+func scaleLanczosTo420(_ context: ComputeContext, srcs: [PictureSample], rungs: [[PictureSample]]) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for src in srcs {
+        guard let image = src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        sources.append(desc)
+    }
+    for rung in rungs {
+        guard rung.count == srcs.count else { throw ComputeError.invalidValue }
+        for target in rung {
+            guard let targetImage = target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            targets.append(targetDesc)
+        }
+    }
+    try check(chv_scale_lanczos_to_420_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
+    return context
+}
 #endif

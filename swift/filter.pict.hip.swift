@@ -33,6 +33,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                 colorspace: Int32 = 0,
                 convert420: Bool = false,
                 convertToRgb: Bool = false,
+                convertDecoderFormats: Bool = false,
                 computeContext: ComputeContext? = nil) {
         self.clock = clock
         self.outputSize = outputSize
@@ -42,6 +43,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
         self.colorspace = colorspace
         self.convert420 = convert420
         self.convertToRgb = convertToRgb
+        self.convertDecoderFormats = convertDecoderFormats
         do {
             if let context = computeContext {
                 self.context = createComputeContext(sharing: context)
@@ -75,6 +77,10 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                         let yuvIn = src.pixelFormat() == .nv12 || src.pixelFormat() == .y420p
                         if strongSelf.convert420 && yuvIn && (format == .nv12 || format == .y420p) && src.pixelFormat() != format {
                             return try scaleLanczos420($0, src: src, target: dst)
+                        }
+                        let decoderIn = [PixelFormat.nv21, .y422p, .y444p, .yuvs, .zvuy].contains(src.pixelFormat())
+                        if strongSelf.convertDecoderFormats && decoderIn && (format == .nv12 || format == .y420p) {
+                            return try scaleLanczosTo420($0, src: src, target: dst)
                         }
                         if strongSelf.convertToRgb && yuvIn && (format == .BGRA || format == .RGBA) {
                             return try scaleLanczosFromYuv($0, src: src, target: dst, colorspace: strongSelf.colorspace)
@@ -143,6 +149,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
     let colorspace: Int32      // chv_colorspace of the integer matrix (the Lanczos conversion)
     let convert420: Bool       // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
     let convertToRgb: Bool     // the Lanczos scaler takes nv12 / y420p -> BGRA / RGBA (off: the pair is an error, as it was)
+    let convertDecoderFormats: Bool      // the Lanczos scaler takes nv21 / y422p / y444p / yuvs / zvuy -> nv12 / y420p (off: an error, as it was)
     var context: ComputeContext?
 }
 #endif

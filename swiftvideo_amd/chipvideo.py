@@ -138,6 +138,8 @@ _SIGNATURES = {
     "chv_scale_lanczos_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
     "chv_scale_lanczos_420": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image)]),
     "chv_scale_lanczos_420_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
+    "chv_scale_lanczos_to_420": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image)]),
+    "chv_scale_lanczos_to_420_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
     "chv_scale_lanczos_from_yuv": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.POINTER(KernelOpts)]),
     "chv_scale_lanczos_from_yuv_batch": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.c_int, C.POINTER(KernelOpts)]),
     "chv_scale_lanczos_from_yuv_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int, C.POINTER(KernelOpts)]),

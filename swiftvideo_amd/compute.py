@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "scaleLanczosRgbLadder", "LanczosRgbLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosTo420", "scaleLanczosTo420Ladder", "LanczosTo420Ladder", "decoderFramePlanes", "pictureFromDecoderFrame", "DECODER_FORMATS", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "scaleLanczosRgbLadder", "LanczosRgbLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -215,6 +215,52 @@ def planesForFormat(fmt, size):
         return [Plane((w, h), w, 8, ["y"]), Plane((w // 2, h // 2), w // 2, 8, ["cb"]),
                 Plane((w // 2, h // 2), w // 2, 8, ["cr"])]
     raise ComputeError(5, "Invalid pixel format")
+
+
+DECODER_FORMATS = (PixelFormat.nv21, PixelFormat.yuvs, PixelFormat.zvuy, PixelFormat.y422p, PixelFormat.y444p)
+
+
+def decoderFramePlanes(fmt, size, strides=None):
+    """The planes of a decoder frame of one of the five formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p), as
+    framePlanes / planeSize describe them (dec.video.ffmpeg.swift:162-185): plane sizes as there, strides from `strides` (the frame's
+    linesize array; packed rows when None).  A packed 4:2:2 plane is the picture's width x height with two bytes per pixel — yuvs: Y0 Cb Y1 Cr,
+    zvuy: Cb Y0 Cr Y1, FFmpeg's YUYV422 / UYVY422 — which is what chv_scale_lanczos_to_420 takes (include/chipvideo.h)."""
+    w, h = int(size[0]), int(size[1])
+    if fmt == PixelFormat.nv21:
+        planes = [Plane((w, h), w, 8, ["y"]), Plane((w // 2, h // 2), w // 2 * 2, 8, ["cr", "cb"])]
+    elif fmt == PixelFormat.yuvs:
+        planes = [Plane((w, h), 2 * w, 8, ["y", "c"])]
+    elif fmt == PixelFormat.zvuy:
+        planes = [Plane((w, h), 2 * w, 8, ["c", "y"])]
+    elif fmt == PixelFormat.y422p:
+        planes = [Plane((w, h), w, 8, ["y"]), Plane((w // 2, h), w // 2, 8, ["cb"]), Plane((w // 2, h), w // 2, 8, ["cr"])]
+    elif fmt == PixelFormat.y444p:
+        planes = [Plane((w, h), w, 8, ["y"]), Plane((w, h), w, 8, ["cb"]), Plane((w, h), w, 8, ["cr"])]
+    else:
+        raise ComputeError(5, "Invalid pixel format")
+    if strides is not None:
+        if len(strides) < len(planes):
+            raise ComputeError(5, f"{len(planes)} planes, {len(strides)} strides")
+        for p, stride in zip(planes, strides):
+            if int(stride) < p.size[0] * len(p.components):
+                raise ComputeError(5, f"stride {stride} is shorter than a row of {p.size[0] * len(p.components)} bytes")
+            p.stride = int(stride)
+    return planes
+
+
+def pictureFromDecoderFrame(fmt, size, arrays, strides=None, **kw):
+    """A CPU PictureSample over the plane arrays of a decoder frame of one of DECODER_FORMATS (decoderFramePlanes says how they are shaped;
+    `arrays[i]` holds rows of strides[i] bytes).  uploadComputePicture and downloadComputePicture carry it like any other picture."""
+    planes = decoderFramePlanes(fmt, size, strides)
+    bufs = []
+    for p, a in zip(planes, arrays):
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(max(p.size[1], 1), -1)
+        if strides is None:
+            p.stride = a.shape[1]
+        elif a.shape[1] != p.stride:
+            raise ComputeError(5, f"plane rows of {a.shape[1]} bytes, stride {p.stride}")
+        bufs.append(a)
+    return PictureSample(ImageBuffer(fmt, "cpu", size, buffers=bufs, planes=planes), **kw)
 
 
 class ImageBuffer:
@@ -873,6 +919,34 @@ def scaleLanczos420Ladder(ctx, rungs, srcs):
     return Lanczos420Ladder(rungs, srcs).run(ctx)
 
 
+def scaleLanczosTo420(ctx, dst, src):
+    """Lanczos-3 resize of a decoder picture of ANY of its seven YUV formats (nv21, y422p, y444p, yuvs, zvuy; nv12 and y420p are forwarded to
+    scaleLanczos420) into an nv12 or y420p picture (chv_scale_lanczos_to_420): the logical images Y, Cb and Cr
+    resampled one by one as scaleLanczos resamples a 1-component plane, stored in the target's packing — no colour arithmetic, no re-siting."""
+    d, s = _image_desc(dst), _image_desc(src)
+    if d is None:
+        raise ComputeError(4, "target has no GPU image buffer")
+    if s is None:
+        raise ComputeError(5, "Bad input image")
+    cv.check(cv.load().chv_scale_lanczos_to_420(ctx.handle, C.byref(d), C.byref(s)))
+    return ctx
+
+
+class LanczosTo420Ladder(LanczosLadder):
+    """LanczosLadder whose sources have any of the decoder's seven YUV formats (chv_scale_lanczos_to_420_ladder): one
+    format for all sources, nv12 or y420p for all targets; one launch per route per chunk, the bytes of the single scaleLanczosTo420 calls."""
+
+    def run(self, ctx):
+        cv.check(cv.load().chv_scale_lanczos_to_420_ladder(ctx.handle, self._d, self.n_rungs, self._s, self.n))
+        return ctx
+
+
+def scaleLanczosTo420Ladder(ctx, rungs, srcs):
+    """Every nv12 or y420p rendition of one or several decoder pictures of one size and one format (chv_scale_lanczos_to_420_ladder):
+    rungs[r][i] receives what scaleLanczosTo420(ctx, rungs[r][i], srcs[i]) would write."""
+    return LanczosTo420Ladder(rungs, srcs).run(ctx)
+
+
 # ---- pipeline operators -----------------------------------------------------------------------
 def scaleLanczosFromYuv(ctx, dst, src, colorspace=cv.CSC_BT601_LIMITED):
     """Lanczos-3 resize of the nv12 or y420p picture `src` into one BGRA or RGBA plane `dst`, in one launch (chv_scale_lanczos_from_yuv,
@@ -980,7 +1054,8 @@ class PictureFilter:
     composite kernels: colour conversion + bilinear scale in one launch (`scaler="bilinear"`, any format
     pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p
     without a conversion, a 4:2:0 picture plane by plane; BGRA or RGBA -> nv12 or y420p through the integer matrix, scaleLanczosToYuv;
-    with `convert420=True` also nv12 <-> y420p, scaleLanczos420, and with `convertToRgb=True` also nv12 or y420p -> BGRA or RGBA through the
+    with `convert420=True` also nv12 <-> y420p, scaleLanczos420, with `convertDecoderFormats=True` also nv21, y422p, y444p, yuvs or zvuy
+    -> nv12 or y420p, scaleLanczosTo420, and with `convertToRgb=True` also nv12 or y420p -> BGRA or RGBA through the
     integer matrix, scaleLanczosFromYuv — both off by default: a host that did not ask for a conversion gets the error it got).
     CPU samples are uploaded first; the sample's time stamps, ids and transform state are carried over.
     Results land in a ring of `numberBackingImages` device images like the mixer's (mix.video.swift:148-167)."""
@@ -988,11 +1063,12 @@ class PictureFilter:
     numberBackingImages = 10
 
     def __init__(self, outputSize, outputFormat=PixelFormat.BGRA, computeContext=None, scaler="bilinear",
-                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False, convertToRgb=False):
+                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False, convertToRgb=False, convertDecoderFormats=False):
         """integerMatrix: an RGB picture converted to a 4:2:0 format goes through the integer BT.601/709 matrix of `colorspace`
         (img_*_int, DESIGN.md 4.5: what an encoder expects); False selects the reference's own float kernels (img_bgra_nv12 ...,
         full range, kernels.cl.swift:96-99)."""
         self.integerMatrix, self.convert420, self.convertToRgb = integerMatrix, convert420, convertToRgb
+        self.convertDecoderFormats = convertDecoderFormats
         if scaler not in ("bilinear", "lanczos"):
             raise ComputeError(0, f"unknown scaler {scaler!r}")
         try:
@@ -1037,6 +1113,9 @@ class PictureFilter:
                 scaleLanczosToYuv(ctx, dst, src, self.colorspace)       # (the float full-range matrix has no Lanczos form)
             elif self.scaler == "lanczos" and self.convert420 and {src.pixelFormat(), self.outputFormat} == {PixelFormat.nv12, PixelFormat.y420p}:
                 scaleLanczos420(ctx, dst, src)
+            elif self.scaler == "lanczos" and self.convertDecoderFormats and src.pixelFormat() in DECODER_FORMATS \
+                    and self.outputFormat in (PixelFormat.nv12, PixelFormat.y420p):
+                scaleLanczosTo420(ctx, dst, src)
             elif self.scaler == "lanczos" and self.convertToRgb and src.pixelFormat() in (PixelFormat.nv12, PixelFormat.y420p) \
                     and self.outputFormat in (PixelFormat.BGRA, PixelFormat.RGBA):
                 scaleLanczosFromYuv(ctx, dst, src, self.colorspace)

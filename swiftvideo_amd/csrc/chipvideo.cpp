@@ -31,6 +31,7 @@
 #include "lanczos_ladder.h"
 #include "lanczos_planar_ladder.h"
 #include "lanczos_420.h"
+#include "lanczos_to_420.h"
 #include "lanczos_from_yuv.h"
 #include "lanczos_from_yuv_ladder.h"
 #include "lanczos_rgb_ladder.h"
@@ -136,6 +137,9 @@ void chv::register_lanczos_planar_ladder_launcher(LanczosPlanarLadderLauncher fn
 // and for the cross pairs of chv_scale_lanczos_420 / chv_scale_lanczos_420_ladder (lanczos_420.h, kernels_lanczos_420.hip.cpp)
 static std::atomic<Lanczos420Launcher> g_lanczos_420_launcher{nullptr};
 void chv::register_lanczos_420_launcher(Lanczos420Launcher fn) { g_lanczos_420_launcher.store(fn, std::memory_order_release); }
+// and for the five other decoder formats of chv_scale_lanczos_to_420 / chv_scale_lanczos_to_420_ladder (lanczos_to_420.h, kernels_lanczos_to_420.hip.cpp)
+static std::atomic<LanczosTo420Launcher> g_lanczos_to_420_launcher{nullptr};
+void chv::register_lanczos_to_420_launcher(LanczosTo420Launcher fn) { g_lanczos_to_420_launcher.store(fn, std::memory_order_release); }
 // and for chv_scale_lanczos_from_yuv / chv_scale_lanczos_from_yuv_batch (lanczos_from_yuv.h, kernels_lanczos_from_yuv.hip.cpp)
 static std::atomic<LanczosFromYuvLauncher> g_lanczos_from_yuv_launcher{nullptr};
 void chv::register_lanczos_from_yuv_launcher(LanczosFromYuvLauncher fn) { g_lanczos_from_yuv_launcher.store(fn, std::memory_order_release); }
@@ -169,6 +173,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "stream_phased_launches")) { *value = debug_counters().stream_phased_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_to_420_launches")) { *value = debug_counters().lanczos_to_420_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_launches")) { *value = debug_counters().lanczos_from_yuv_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_ladder_launches")) { *value = debug_counters().lanczos_from_yuv_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_rgb_ladder_launches")) { *value = debug_counters().lanczos_rgb_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
@@ -2786,6 +2791,115 @@ extern "C" int chv_scale_lanczos_420(chv_context *c, const chv_image *dst, const
     if (rc) return rc;
     // a same-format pair is chv_scale_lanczos's; a cross pair is the ladder of one rung and one picture
     return dnp == snp ? chv_scale_lanczos(c, dst, src) : chv_scale_lanczos_420_ladder(c, dst, 1, src, 1);
+}
+
+// ---- chv_scale_lanczos_to_420 / chv_scale_lanczos_to_420_ladder: the decoder's other five formats -> NV12 / y420p ----
+static_assert(lanczos_chunk(4 * 2 + 1) == CHV_420_LADDER_CHUNK(4, 2, 1) && lanczos_chunk(8 * 3 + 3) >= 1, "a chunk is what fits one descriptor slot");
+
+// planes of a source of one of the five formats, 0 for every other (format, structure); *kind: LanczosTo420Source
+static int lanczos_to_420_kind(const chv_image *img, int *kind) {
+    if (!img) return 0;
+    switch (img->format) {
+    case CHV_FMT_NV21: *kind = kTo420Nv21; return img->n_planes == 2 ? 2 : 0;
+    case CHV_FMT_Y422P: case CHV_FMT_Y444P: *kind = kTo420Planar; return img->n_planes == 3 ? 3 : 0;
+    case CHV_FMT_YUVS: *kind = kTo420Yuvs; return img->n_planes == 1 ? 1 : 0;
+    case CHV_FMT_ZVUY: *kind = kTo420Zvuy; return img->n_planes == 1 ? 1 : 0;
+    default: return 0;
+    }
+}
+
+// every plane of one source of the five formats -> out[0 .. np), every check of plane_to_device on every plane; Cb and Cr must agree, a packed
+// plane (2 bytes per pixel) must have an even width
+static int lanczos_to_420_planes(chv_context *c, const chv_image *img, int np, int kind, int idx, DPlane *out) {
+    int k2 = 0;
+    if (lanczos_to_420_kind(img, &k2) != np || k2 != kind)
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos to 4:2:0: source %d must be nv21 (2 planes), y422p / y444p (3), yuvs / zvuy (1), nv12 or y420p", idx);
+    for (int p = 0; p < np; p++) {
+        const int comps = kind == kTo420Planar ? 1 : kind == kTo420Nv21 ? (p ? 2 : 1) : 2;
+        int rc = plane_to_device(img->planes[p], comps, c->device, &out[p], CHV_ERR_BAD_INPUT, "input", p);
+        if (rc) return rc;
+    }
+    if (np == 3 && (out[1].w != out[2].w || out[1].h != out[2].h))
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos to 4:2:0: source %d: chroma planes of %dx%d and %dx%d (Cb and Cr have one size)", idx, out[1].w, out[1].h, out[2].w, out[2].h);
+    if (np == 1 && (out[0].w & 1))
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos to 4:2:0: source %d: a packed 4:2:2 picture of odd width %d", idx, out[0].w);
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_to_420_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
+    const LanczosTo420Launcher launcher = g_lanczos_to_420_launcher.load(std::memory_order_acquire);
+    const int dnp = lanczos_planar_planes(&dsts[0]);
+    if (!dnp) return fail(CHV_ERR_BAD_TARGET, "Lanczos to 4:2:0: target 0 must be nv12 with 2 planes or y420p with 3");
+    // NV12 and y420p sources are chv_scale_lanczos_420_ladder's: its checks, its launchers, its counters, its bytes
+    if (lanczos_planar_planes(&srcs[0])) return chv_scale_lanczos_420_ladder(c, dsts, n_rungs, srcs, n);
+    int kind = 0;
+    const int snp = lanczos_to_420_kind(&srcs[0], &kind);
+    if (!snp) return fail(CHV_ERR_BAD_INPUT, "Lanczos to 4:2:0: source 0 must be nv21 (2 planes), y422p / y444p (3), yuvs / zvuy (1), nv12 or y420p");
+    rc = lanczos_ladder_formats(dsts, n_rungs, srcs, n);
+    if (rc) return rc;
+    // a picture's record: the dnp target planes of rung 0, of rung 1, ..., then the snp source planes
+    const size_t per = (size_t)n_rungs * dnp + snp, src_at = (size_t)n_rungs * dnp;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        int np = 0;
+        for (int r = 0; r < n_rungs; r++) {
+            rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
+            if (rc) return rc;
+            for (int p = 0; p < dnp; p++)
+                if (pi[r * dnp + p].w != planes[r * dnp + p].w || pi[r * dnp + p].h != planes[r * dnp + p].h)
+                    return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p,
+                                pi[r * dnp + p].w, pi[r * dnp + p].h, planes[r * dnp + p].w, planes[r * dnp + p].h);
+        }
+        rc = lanczos_to_420_planes(c, &srcs[i], snp, kind, i, pi + src_at);
+        if (rc) return rc;
+        for (int p = 0; p < snp; p++)
+            if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
+                return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
+                            pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
+    }
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no to-4:2:0 Lanczos kernels"));
+    if (rc) return rc;
+    // two tables per logical image per rung
+    LanczosRef refs[2 * kLanczosPlanarMaxPlanes * CHV_LADDER_MAX_RUNGS];
+    LanczosTo420Job job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs; job.source = kind; job.dst_planes = dnp; job.src_planes = snp;
+    job.luma_w = planes[src_at].w; job.luma_h = planes[src_at].h;
+    // a packed plane's chroma images are width / 2 x height; every other source says their size itself
+    job.chroma_w = snp == 1 ? planes[src_at].w / 2 : planes[src_at + 1].w;
+    job.chroma_h = snp == 1 ? planes[src_at].h : planes[src_at + 1].h;
+    for (int r = 0; r < n_rungs; r++) {
+        for (int p = 0; p < dnp; p++) {
+            const DPlane &d = planes[r * dnp + p];
+            LanczosRef *rp = &refs[2 * (r * kLanczosPlanarMaxPlanes + p)];
+            rc = lanczos_table_pair(c, p ? job.chroma_w : job.luma_w, p ? job.chroma_h : job.luma_h, d.w, d.h, &rp[0], &rp[1], &job.rung[r].tab[p]);
+            if (rc) return rc;
+            job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
+        }
+    }
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
+        job.batch = dev; job.n_pictures = m;
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_to_420_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        return e != hipSuccess ? hip_fail(e, "lanczos to 4:2:0 launch") : CHV_OK;
+    });
+}
+
+extern "C" int chv_scale_lanczos_to_420(chv_context *c, const chv_image *dst, const chv_image *src) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (!lanczos_planar_planes(dst)) return fail(CHV_ERR_BAD_TARGET, "Lanczos to 4:2:0: the target must be nv12 with 2 planes or y420p with 3");
+    if (!src) return fail(CHV_ERR_BAD_INPUT, "Lanczos to 4:2:0: null source");
+    // an NV12 or y420p source is chv_scale_lanczos_420's; everything else is the ladder of one rung and one picture
+    return lanczos_planar_planes(src) ? chv_scale_lanczos_420(c, dst, src) : chv_scale_lanczos_to_420_ladder(c, dst, 1, src, 1);
 }
 
 // ---- chv_scale_lanczos_from_yuv: an NV12 or y420p picture -> one BGRA / RGBA plane ----

@@ -243,6 +243,28 @@ inline std::vector<Plane> planesForFormat(PixelFormat f, Vector2 size) {
     }
 }
 
+// The planes of a decoder frame of one of the five formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p), as framePlanes /
+// planeSize describe them (dec.video.ffmpeg.swift:162-185): plane sizes as there, strides from the frame's linesize array (packed rows when
+// null).  A packed 4:2:2 plane is the picture's width x height at two bytes per pixel (yuvs: Y0 Cb Y1 Cr, zvuy: Cb Y0 Cr Y1), which is what
+// chv_scale_lanczos_to_420 takes.
+inline std::vector<Plane> decoderFramePlanes(PixelFormat f, Vector2 size, const int *strides = nullptr) {
+    const int w = (int)size.x, h = (int)size.y;
+    std::vector<Plane> planes;
+    const Vector2 half{ (float)(w / 2), (float)(h / 2) }, halfw{ (float)(w / 2), (float)h };
+    switch (f) {
+    case PixelFormat::nv21: planes = { Plane{ size, w, 8, 1 }, Plane{ half, w / 2 * 2, 8, 2 } }; break;
+    case PixelFormat::yuvs: case PixelFormat::zvuy: planes = { Plane{ size, 2 * w, 8, 2 } }; break;
+    case PixelFormat::y422p: planes = { Plane{ size, w, 8, 1 }, Plane{ halfw, w / 2, 8, 1 }, Plane{ halfw, w / 2, 8, 1 } }; break;
+    case PixelFormat::y444p: planes = { Plane{ size, w, 8, 1 }, Plane{ size, w, 8, 1 }, Plane{ size, w, 8, 1 } }; break;
+    default: throw ComputeError(CHV_ERR_BAD_INPUT, "Invalid pixel format");
+    }
+    for (size_t i = 0; strides && i < planes.size(); i++) {
+        if (strides[i] < (int)planes[i].size.x * planes[i].components) throw ComputeError(CHV_ERR_BAD_INPUT, "stride shorter than a row");
+        planes[i].stride = strides[i];
+    }
+    return planes;
+}
+
 struct PictureSample {
     std::shared_ptr<ImageBuffer> img;
     Matrix4 matrix, textureMatrix, borderMatrix;
@@ -664,6 +686,33 @@ inline ComputeContext scaleLanczos420(ComputeContext ctx, const std::vector<std:
     return ctx;
 }
 
+// Lanczos-3 from any of the decoder's seven YUV formats into an nv12 or y420p picture (chv_scale_lanczos_to_420): nv21,
+// y422p, y444p, yuvs and zvuy sources — nv12 and y420p are forwarded to scaleLanczos420 — with the logical images Y, Cb and Cr resampled one by
+// one as scaleLanczos resamples a 1-component plane and stored in the target's packing; no colour arithmetic, no re-siting.
+inline ComputeContext scaleLanczosTo420(ComputeContext ctx, const PictureSample &dst, const PictureSample &src) {
+    chv_image d, s;
+    if (!describe(dst, &d)) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    if (!describe(src, &s)) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    check(chv_scale_lanczos_to_420(ctx.get(), &d, &s));
+    return ctx;
+}
+
+// The ladder of it (chv_scale_lanczos_to_420_ladder): rungs[r][i] receives what scaleLanczosTo420(ctx, rungs[r][i], srcs[i]) would write — one
+// format and one size for all sources, nv12 or y420p for all targets; one launch per route per chunk.
+inline ComputeContext scaleLanczosTo420(ComputeContext ctx, const std::vector<std::vector<PictureSample>> &rungs, const std::vector<PictureSample> &srcs) {
+    const size_t n = srcs.size();
+    std::vector<chv_image> d(rungs.size() * n), s(n);
+    for (size_t i = 0; i < n; i++)
+        if (!describe(srcs[i], &s[i])) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    for (size_t r = 0; r < rungs.size(); r++) {
+        if (rungs[r].size() != n) throw ComputeError(CHV_ERR_INVALID_VALUE, "a rung has one target per source");
+        for (size_t i = 0; i < n; i++)
+            if (!describe(rungs[r][i], &d[r * n + i])) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    }
+    check(chv_scale_lanczos_to_420_ladder(ctx.get(), d.data(), (int)rungs.size(), s.data(), (int)n));
+    return ctx;
+}
+
 // Many independent ticks as ONE launch (chv_batch_*): what a host with several mixers / streams on a device
 // (composer.swift:203-224) uses instead of one chv_composite per tick; byte-identical to running them one by one.
 struct Tick { PictureSample target; bool clearFirst = true; std::vector<TickLayer> layers; };
@@ -938,7 +987,8 @@ private:
 //      (filter.pict.swift:20-47).  Converts a picture to outputFormat at outputSize on the device: one
 //      full-canvas layer through the composite kernels (colour conversion + bilinear scale in one launch),
 //      or a separable Lanczos-3 resample (BGRA -> BGRA, nv12 -> nv12, y420p -> y420p without a conversion; BGRA or RGBA -> nv12 or y420p through
-//      the integer matrix, scaleLanczosToYuv; with convert420 set also nv12 <-> y420p, scaleLanczos420; with convertToRgb set also nv12 or y420p ->
+//      the integer matrix, scaleLanczosToYuv; with convert420 set also nv12 <-> y420p, scaleLanczos420; with convertDecoderFormats set
+//      also nv21, y422p, y444p, yuvs or zvuy -> nv12 or y420p, scaleLanczosTo420; with convertToRgb set also nv12 or y420p ->
 //      BGRA or RGBA through the integer matrix, scaleLanczosFromYuv).  CPU samples are uploaded first; results land in a
 //      ring of device images like the mixer's (mix.video.swift:148-167). ------------------------------------
 class PictureFilter {
@@ -961,6 +1011,7 @@ public:
     bool integerMatrix = true;
     bool convert420 = false;          // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
     bool convertToRgb = false;        // the Lanczos scaler takes nv12 or y420p -> BGRA or RGBA (off: the pair is an error, as it was)
+    bool convertDecoderFormats = false;      // the Lanczos scaler takes nv21, y422p, y444p, yuvs or zvuy -> nv12 or y420p (off: an error, as it was)
 
     EventBox<PictureSample> operator()(const PictureSample &sample) {
         EventBox<PictureSample> r;
@@ -975,6 +1026,10 @@ public:
                        (src.pixelFormat() == PixelFormat::nv12 || src.pixelFormat() == PixelFormat::y420p) &&
                        (format_ == PixelFormat::nv12 || format_ == PixelFormat::y420p)) {
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczos420(c, dst, src); });
+            } else if (scaler_ == Scaler::lanczos && convertDecoderFormats && (format_ == PixelFormat::nv12 || format_ == PixelFormat::y420p) &&
+                       (src.pixelFormat() == PixelFormat::nv21 || src.pixelFormat() == PixelFormat::y422p || src.pixelFormat() == PixelFormat::y444p ||
+                        src.pixelFormat() == PixelFormat::yuvs || src.pixelFormat() == PixelFormat::zvuy)) {
+                usingContext(context_, [&](ComputeContext c) { return scaleLanczosTo420(c, dst, src); });
             } else if (scaler_ == Scaler::lanczos && convertToRgb && (src.pixelFormat() == PixelFormat::nv12 || src.pixelFormat() == PixelFormat::y420p) &&
                        (format_ == PixelFormat::BGRA || format_ == PixelFormat::RGBA)) {
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczosFromYuv(c, dst, src, colorspace_); });
