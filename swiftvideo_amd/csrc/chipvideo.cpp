@@ -2291,6 +2291,15 @@ static int lanczos_ladder_formats(const chv_image *dsts, int n_rungs, const chv_
     return CHV_OK;
 }
 
+// the snp planes of source i have the sizes of the ladder's first source
+static int lanczos_one_source_size(const DPlane *src, const DPlane *first, int snp, int i) {
+    for (int p = 0; p < snp; p++)
+        if (src[p].w != first[p].w || src[p].h != first[p].h)
+            return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, src[p].w, src[p].h,
+                        first[p].w, first[p].h);
+    return CHV_OK;
+}
+
 // ---- the 4:2:0 families of chv_scale_lanczos: NV12 (planes of 1 and 2 components) and y420p (three planes of 1), plane by plane ----
 // Pictures per descriptor slot of a batch chunk: a picture's np plane pairs, lanczos_chunk(2 * np).
 static_assert(lanczos_chunk(4) == 62 && lanczos_chunk(6) == 41, "include/chipvideo.h states the counts");
@@ -2664,10 +2673,8 @@ extern "C" int chv_scale_lanczos_ladder(chv_context *c, const chv_image *dsts, i
                                 pairs[2 * p].h, d0.w, d0.h);
             }
         }
-        for (int p = 0; p < np; p++)
-            if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
-                return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
-                            pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
+        rc = lanczos_one_source_size(pi + src_at, planes.data() + src_at, np, i);
+        if (rc) return rc;
     }
     rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no planar Lanczos ladder kernels"));
     if (rc) return rc;
@@ -2717,6 +2724,35 @@ static int lanczos_420_planes(chv_context *c, const chv_image *img, int err, con
     return CHV_OK;
 }
 
+// Picture i's target planes, rung by rung -> pi[r * dnp + p]; every plane has the size of its place in the ladder's first picture (`first`)
+static int lanczos_420_targets(chv_context *c, const chv_image *dsts, int n_rungs, int n, int i, int dnp, DPlane *pi, const DPlane *first) {
+    int np = 0;
+    for (int r = 0; r < n_rungs; r++) {
+        int rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
+        if (rc) return rc;
+        for (int p = 0; p < dnp; p++)
+            if (pi[r * dnp + p].w != first[r * dnp + p].w || pi[r * dnp + p].h != first[r * dnp + p].h)
+                return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p,
+                            pi[r * dnp + p].w, pi[r * dnp + p].h, first[r * dnp + p].w, first[r * dnp + p].h);
+    }
+    return CHV_OK;
+}
+
+// job->rung[r]: two tables per target plane — from the job's logical luma or chroma size to the plane's in the first picture — and that size
+template <class Job>
+static int lanczos_420_tables(chv_context *c, const DPlane *planes, int n_rungs, int dnp, LanczosRef *refs, Job *job) {
+    for (int r = 0; r < n_rungs; r++) {
+        for (int p = 0; p < dnp; p++) {
+            const DPlane &d = planes[r * dnp + p];
+            LanczosRef *rp = &refs[2 * (r * kLanczosPlanarMaxPlanes + p)];
+            int rc = lanczos_table_pair(c, p ? job->chroma_w : job->luma_w, p ? job->chroma_h : job->luma_h, d.w, d.h, &rp[0], &rp[1], &job->rung[r].tab[p]);
+            if (rc) return rc;
+            job->rung[r].w[p] = d.w; job->rung[r].h[p] = d.h;
+        }
+    }
+    return CHV_OK;
+}
+
 extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
     if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
     FLUSH_PENDING(c);
@@ -2735,21 +2771,13 @@ extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dst
     DepScope deps;
     for (int i = 0; i < n; i++) {
         DPlane *pi = planes.data() + per * i;
+        rc = lanczos_420_targets(c, dsts, n_rungs, n, i, dnp, pi, planes.data());
+        if (rc) return rc;
         int np = 0;
-        for (int r = 0; r < n_rungs; r++) {
-            rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
-            if (rc) return rc;
-            for (int p = 0; p < dnp; p++)
-                if (pi[r * dnp + p].w != planes[r * dnp + p].w || pi[r * dnp + p].h != planes[r * dnp + p].h)
-                    return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p,
-                                pi[r * dnp + p].w, pi[r * dnp + p].h, planes[r * dnp + p].w, planes[r * dnp + p].h);
-        }
         rc = lanczos_420_planes(c, &srcs[i], CHV_ERR_BAD_INPUT, "input", i, pi + src_at, &np);
         if (rc) return rc;
-        for (int p = 0; p < snp; p++)
-            if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
-                return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
-                            pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
+        rc = lanczos_one_source_size(pi + src_at, planes.data() + src_at, snp, i);
+        if (rc) return rc;
     }
     // same-format lists are chv_scale_lanczos_ladder's: its launchers, its counter, its bytes
     if (dnp == snp) return chv_scale_lanczos_ladder(c, dsts, n_rungs, srcs, n);
@@ -2762,15 +2790,8 @@ extern "C" int chv_scale_lanczos_420_ladder(chv_context *c, const chv_image *dst
     job.n_rungs = n_rungs; job.dst_planes = dnp; job.src_planes = snp;
     job.luma_w = planes[src_at].w; job.luma_h = planes[src_at].h;
     job.chroma_w = planes[src_at + 1].w; job.chroma_h = planes[src_at + 1].h;
-    for (int r = 0; r < n_rungs; r++) {
-        for (int p = 0; p < dnp; p++) {
-            const DPlane &d = planes[r * dnp + p];
-            LanczosRef *rp = &refs[2 * (r * kLanczosPlanarMaxPlanes + p)];
-            rc = lanczos_table_pair(c, p ? job.chroma_w : job.luma_w, p ? job.chroma_h : job.luma_h, d.w, d.h, &rp[0], &rp[1], &job.rung[r].tab[p]);
-            if (rc) return rc;
-            job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
-        }
-    }
+    rc = lanczos_420_tables(c, planes.data(), n_rungs, dnp, refs, &job);
+    if (rc) return rc;
     return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
         int launches = 0;
@@ -2848,21 +2869,12 @@ extern "C" int chv_scale_lanczos_to_420_ladder(chv_context *c, const chv_image *
     DepScope deps;
     for (int i = 0; i < n; i++) {
         DPlane *pi = planes.data() + per * i;
-        int np = 0;
-        for (int r = 0; r < n_rungs; r++) {
-            rc = lanczos_420_planes(c, &dsts[(size_t)r * n + i], CHV_ERR_BAD_TARGET, "target", r * n + i, pi + r * dnp, &np);
-            if (rc) return rc;
-            for (int p = 0; p < dnp; p++)
-                if (pi[r * dnp + p].w != planes[r * dnp + p].w || pi[r * dnp + p].h != planes[r * dnp + p].h)
-                    return fail(CHV_ERR_INVALID_VALUE, "rung %d, target %d, plane %d is %dx%d, the rung began with %dx%d (one size per rung)", r, i, p,
-                                pi[r * dnp + p].w, pi[r * dnp + p].h, planes[r * dnp + p].w, planes[r * dnp + p].h);
-        }
+        rc = lanczos_420_targets(c, dsts, n_rungs, n, i, dnp, pi, planes.data());
+        if (rc) return rc;
         rc = lanczos_to_420_planes(c, &srcs[i], snp, kind, i, pi + src_at);
         if (rc) return rc;
-        for (int p = 0; p < snp; p++)
-            if (pi[src_at + p].w != planes[src_at + p].w || pi[src_at + p].h != planes[src_at + p].h)
-                return fail(CHV_ERR_INVALID_VALUE, "source %d, plane %d is %dx%d, the ladder began with %dx%d (one source size per ladder)", i, p, pi[src_at + p].w,
-                            pi[src_at + p].h, planes[src_at + p].w, planes[src_at + p].h);
+        rc = lanczos_one_source_size(pi + src_at, planes.data() + src_at, snp, i);
+        if (rc) return rc;
     }
     rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no to-4:2:0 Lanczos kernels"));
     if (rc) return rc;
@@ -2875,15 +2887,8 @@ extern "C" int chv_scale_lanczos_to_420_ladder(chv_context *c, const chv_image *
     // a packed plane's chroma images are width / 2 x height; every other source says their size itself
     job.chroma_w = snp == 1 ? planes[src_at].w / 2 : planes[src_at + 1].w;
     job.chroma_h = snp == 1 ? planes[src_at].h : planes[src_at + 1].h;
-    for (int r = 0; r < n_rungs; r++) {
-        for (int p = 0; p < dnp; p++) {
-            const DPlane &d = planes[r * dnp + p];
-            LanczosRef *rp = &refs[2 * (r * kLanczosPlanarMaxPlanes + p)];
-            rc = lanczos_table_pair(c, p ? job.chroma_w : job.luma_w, p ? job.chroma_h : job.luma_h, d.w, d.h, &rp[0], &rp[1], &job.rung[r].tab[p]);
-            if (rc) return rc;
-            job.rung[r].w[p] = d.w; job.rung[r].h[p] = d.h;
-        }
-    }
+    rc = lanczos_420_tables(c, planes.data(), n_rungs, dnp, refs, &job);
+    if (rc) return rc;
     return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
         job.batch = dev; job.n_pictures = m;
         int launches = 0;

@@ -11,8 +11,7 @@
 //   lanczos_from_yuv_ladder_tile        the rungs that take the tile route, both packings: 256-thread blocks, one per 32 x 4 output pixels.
 #include "lanczos_from_yuv_body.hip.h"
 #include "lanczos_from_yuv_ladder.h"
-
-#include <climits>
+#include "lanczos_ladder_launch.hip.h"
 
 namespace chv {
 
@@ -50,13 +49,6 @@ static_assert(sizeof(FylArgs) <= 4096 - 256, "kernel arguments: 4 KB in all, 256
 
 CHV_DEV uint64_t fyl_opaque(uint64_t v) { asm volatile("" : "+s"(v) :: "memory"); return v; }
 
-CHV_DEV int fyl_rung_of(const FylArgs &a, int b) {
-    int r = 0;
-#pragma unroll
-    for (int k = 1; k < kLanczosPlanarLadderMaxRungs; k++) r = b >= a.first[k] ? k : r;
-    return r;
-}
-
 // rung r's record in the kernel-argument segment; the record of picture `picture` in the descriptor list (both uniform)
 CHV_DEV uint64_t fyl_rung(uint64_t ka, int r) { return ka + offsetof(FylArgs, rung) + (uint64_t)r * sizeof(FylRung); }
 CHV_DEV uint64_t fyl_record(uint64_t ka, int picture) {
@@ -79,7 +71,7 @@ CHV_DEV PlanarPlane fyl_plane(const FyTab &t, int ow, int oh, const DPlane &src)
 template <int MAXT, int SC>
 __global__ __launch_bounds__(64, 4) void lanczos_from_yuv_ladder(const FylArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fy_lsm[];
-    const int r = fyl_rung_of(a, blockIdx.x);
+    const int r = ladder_rung_of(a.first, blockIdx.x);
     uint64_t ka = (uint64_t)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     int picture, chunk, strip, codes_at;
     {
@@ -87,11 +79,10 @@ __global__ __launch_bounds__(64, 4) void lanczos_from_yuv_ladder(const FylArgs a
         const int b = (int)blockIdx.x - cld<int32_t>(R + offsetof(FylRung, first_block));
         const int total = cld<int32_t>(R + offsetof(FylRung, total)), per_picture = cld<int32_t>(R + offsetof(FylRung, per_picture));
         const int strips = cld<int32_t>(R + offsetof(FylRung, strips));
-        const int per_xcd = (total + 7) >> 3;                     // XCD-aware numbering inside the rung's own (padded) range
-        const int idx = (b & 7) * per_xcd + (b >> 3);
-        if ((b >> 3) >= per_xcd || idx >= total) return;
-        picture = idx / per_picture;
-        const int rem = idx - picture * per_picture;
+        const LadderItem it = ladder_item<true>(b, total);        // XCD-aware numbering inside the rung's own (padded) range
+        if (!it.live) return;
+        picture = it.idx / per_picture;
+        const int rem = it.idx - picture * per_picture;
         chunk = rem / strips; strip = rem - chunk * strips;
         codes_at = cld<int32_t>(R + offsetof(FylRung, codes_at));
     }
@@ -144,7 +135,7 @@ __global__ __launch_bounds__(64, 4) void lanczos_from_yuv_ladder(const FylArgs a
 
 __global__ __launch_bounds__(256) void lanczos_from_yuv_ladder_tile(const FylArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fy_lsm[];
-    const int r = fyl_rung_of(a, blockIdx.x);
+    const int r = ladder_rung_of(a.first, blockIdx.x);
     const uint64_t ka = (uint64_t)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
     const uint64_t R = fyl_rung(ka, r);
     const int idx = (int)blockIdx.x - cld<int32_t>(R + offsetof(FylRung, first_block));
@@ -175,24 +166,6 @@ struct FylPending {
     int TL, TC, ring;                 // strip route: the tap classes of luma and chroma, the longest ring slot
     long work;                        // strip route: the (strip, output row) pairs of all pictures
 };
-
-// the records of one launch, largest range first; false when the grid would not fit 30 bits
-static bool fyl_order(FylArgs *a, const FylPending *rungs, int n, int pad, unsigned *grid) {
-    int order[kLanczosPlanarLadderMaxRungs];
-    for (int k = 0; k < n; k++) order[k] = k;
-    std::stable_sort(order, order + n, [&](int x, int y) { return rungs[x].R.total > rungs[y].R.total; });
-    long first = 0;
-    for (int k = 0; k < kLanczosPlanarLadderMaxRungs; k++) a->first[k] = INT_MAX;
-    for (int k = 0; k < n; k++) {
-        a->rung[k] = rungs[order[k]].R;
-        a->rung[k].first_block = (int32_t)first;
-        a->first[k] = (int32_t)first;
-        first += ((long)a->rung[k].total + pad - 1) / pad * pad;
-        if (first > 0x3fffffff) return false;
-    }
-    *grid = (unsigned)first;
-    return true;
-}
 
 static hipError_t launch_lanczos_from_yuv_ladder(const LanczosFromYuvLadderJob &job, hipStream_t stream, int *launches) {
     *launches = 0;
@@ -261,10 +234,11 @@ static hipError_t launch_lanczos_from_yuv_ladder(const LanczosFromYuvLadderJob &
     a.per_image = job.n_rungs + job.src_planes; a.src_at = job.n_rungs;
     FylArgs t = a;
     unsigned strip_grid = 0, tile_grid = 0;
-    if (n_strip && !fyl_order(&a, strip, n_strip, 8, &strip_grid)) return hipErrorInvalidValue;
-    if (n_tile && !fyl_order(&t, tile, n_tile, 1, &tile_grid)) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    if (n_strip) {
+    const auto total = [](const FylPending &P) { return P.R.total; };
+    const auto copy = [](FylArgs *to, int k, const FylPending &P) { to->rung[k] = P.R; };
+    if (n_strip && !ladder_order(&a, strip, n_strip, 8, &strip_grid, total, copy)) return hipErrorInvalidValue;
+    if (n_tile && !ladder_order(&t, tile, n_tile, 1, &tile_grid, total, copy)) return hipErrorInvalidValue;
+    return ladder_launch(launches, n_strip, [&] {
         if (max_tl <= 12) {
             if (nv12) hipLaunchKernelGGL((lanczos_from_yuv_ladder<12, 2>), dim3(strip_grid), dim3(64), strip_lds, stream, a);
             else hipLaunchKernelGGL((lanczos_from_yuv_ladder<12, 1>), dim3(strip_grid), dim3(64), strip_lds, stream, a);
@@ -272,17 +246,7 @@ static hipError_t launch_lanczos_from_yuv_ladder(const LanczosFromYuvLadderJob &
             if (nv12) hipLaunchKernelGGL((lanczos_from_yuv_ladder<22, 2>), dim3(strip_grid), dim3(64), strip_lds, stream, a);
             else hipLaunchKernelGGL((lanczos_from_yuv_ladder<22, 1>), dim3(strip_grid), dim3(64), strip_lds, stream, a);
         }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ++*launches;
-    }
-    if (n_tile) {
-        hipLaunchKernelGGL(lanczos_from_yuv_ladder_tile, dim3(tile_grid), dim3(256), tile_lds, stream, t);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ++*launches;
-    }
-    return hipSuccess;
+    }, n_tile, [&] { hipLaunchKernelGGL(lanczos_from_yuv_ladder_tile, dim3(tile_grid), dim3(256), tile_lds, stream, t); });
 }
 
 // (the pointer in chipvideo.cpp is constant-initialised to null, so the order of the units' initialisers does not matter)

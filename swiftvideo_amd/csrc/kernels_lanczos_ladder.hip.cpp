@@ -17,8 +17,7 @@
 // Dynamic LDS is the maximum over the launch's rungs.
 #include "lanczos_to_yuv_body.hip.h"
 #include "lanczos_ladder.h"
-
-#include <climits>
+#include "lanczos_ladder_launch.hip.h"
 
 namespace chv {
 
@@ -42,14 +41,7 @@ struct LadderArgs {
     LadderRung rung[kLanczosLadderMaxRungs];
 };
 static_assert(sizeof(LadderArgs) <= 1024, "kernel arguments: 4 KB in all");
-
-// the rung whose range holds block b: first[] ascends, first[0] == 0
-CHV_DEV int ladder_rung_of(const LadderArgs &a, int b) {
-    int r = 0;
-#pragma unroll
-    for (int k = 1; k < kLanczosLadderMaxRungs; k++) r = b >= a.first[k] ? k : r;
-    return r;
-}
+static_assert(kLanczosLadderMaxRungs == kLanczosPlanarLadderMaxRungs, "lanczos_ladder_grid.h scans and orders this many rungs");
 
 // picture `image`'s planes for the rung whose targets start at plane `dst_at`: from the descriptor list (scalar loads)
 CHV_DEV ToYuvPlanes ladder_planes(const LadderArgs &a, int image, int dst_at) {
@@ -65,11 +57,11 @@ CHV_DEV ToYuvPlanes ladder_planes(const LadderArgs &a, int image, int dst_at) {
 
 template <int MAXT>
 __global__ __launch_bounds__(64, (MAXT >= 18 ? 3 : 4)) void lanczos_yuv_ladder(const LadderArgs a) {
-    const int r = ladder_rung_of(a, blockIdx.x);
+    const int r = ladder_rung_of(a.first, blockIdx.x);
     const LadderRung &R = a.rung[r];
-    const int b = blockIdx.x - R.first_block, total = R.total, per_xcd = (total + 7) >> 3;       // XCD-aware numbering inside the rung's range
-    const int idx = (b & 7) * per_xcd + (b >> 3);
-    if ((b >> 3) >= per_xcd || idx >= total) return;
+    const LadderItem it = ladder_item<true>(blockIdx.x - R.first_block, R.total);      // XCD-aware numbering inside the rung's range
+    if (!it.live) return;
+    const int idx = it.idx;
     const int per_picture = R.per_picture, strips = R.strips;
     const int image = idx / per_picture, rem = idx - image * per_picture;
     const int chunk = rem / strips, strip = rem - chunk * strips;
@@ -83,34 +75,17 @@ __global__ __launch_bounds__(64, (MAXT >= 18 ? 3 : 4)) void lanczos_yuv_ladder(c
 }
 
 __global__ __launch_bounds__(256) void lanczos_yuv_ladder_tile(const LadderArgs a) {
-    const int r = ladder_rung_of(a, blockIdx.x);
+    const int r = ladder_rung_of(a.first, blockIdx.x);
     const LadderRung &R = a.rung[r];
-    const int idx = blockIdx.x - R.first_block;
-    if (idx >= R.total) return;
+    const LadderItem it = ladder_item<false>(blockIdx.x - R.first_block, R.total);
+    if (!it.live) return;
+    const int idx = it.idx;
     const int per_picture = R.per_picture, strips = R.strips;
     const int image = idx / per_picture, rem = idx - image * per_picture;
     const int by = rem / strips, bx = rem - by * strips;
     const ToYuvPlanes P = ladder_planes(a, image, R.dst_at);
     lanczos_yuv_tile_body(a, P, R, by, bx);
 }
-
-// the records of one launch, largest range first; false when the grid would not fit 30 bits
-static bool ladder_order(LadderArgs *a, const LadderRung *rungs, int n, int pad) {
-    int order[kLanczosLadderMaxRungs];
-    for (int k = 0; k < n; k++) order[k] = k;
-    std::stable_sort(order, order + n, [&](int x, int y) { return rungs[x].total > rungs[y].total; });
-    long first = 0;
-    for (int k = 0; k < kLanczosLadderMaxRungs; k++) a->first[k] = INT_MAX;
-    for (int k = 0; k < n; k++) {
-        a->rung[k] = rungs[order[k]];
-        a->rung[k].first_block = (int32_t)first;
-        a->first[k] = (int32_t)first;
-        first += ((long)a->rung[k].total + pad - 1) / pad * pad;
-        if (first > 0x3fffffff) return false;
-    }
-    return true;
-}
-static unsigned ladder_grid(const LadderArgs &a, int n, int pad) { return (unsigned)(a.rung[n - 1].first_block + (a.rung[n - 1].total + pad - 1) / pad * pad); }
 
 static hipError_t launch_lanczos_ladder(const LanczosLadderJob &job, hipStream_t stream, int *launches) {
     *launches = 0;
@@ -165,24 +140,13 @@ static hipError_t launch_lanczos_ladder(const LanczosLadderJob &job, hipStream_t
     a.ku0 = job.ku[0]; a.ku1 = job.ku[1]; a.ku2 = job.ku[2];
     a.kv0 = job.kv[0]; a.kv1 = job.kv[1]; a.kv2 = job.kv[2];
     LadderArgs t = a;
-    if (n_strip && !ladder_order(&a, strip, n_strip, 8)) return hipErrorInvalidValue;
-    if (n_tile && !ladder_order(&t, tile, n_tile, 1)) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    if (n_strip) {
-        const dim3 grid(ladder_grid(a, n_strip, 8));
-        if (max_t <= 16) hipLaunchKernelGGL(lanczos_yuv_ladder<16>, grid, dim3(64), strip_lds, stream, a);
-        else hipLaunchKernelGGL(lanczos_yuv_ladder<22>, grid, dim3(64), strip_lds, stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ++*launches;
-    }
-    if (n_tile) {
-        hipLaunchKernelGGL(lanczos_yuv_ladder_tile, dim3(ladder_grid(t, n_tile, 1)), dim3(256), tile_lds, stream, t);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ++*launches;
-    }
-    return hipSuccess;
+    unsigned strip_grid = 0, tile_grid = 0;
+    if (n_strip && !ladder_order(&a, strip, n_strip, 8, &strip_grid)) return hipErrorInvalidValue;
+    if (n_tile && !ladder_order(&t, tile, n_tile, 1, &tile_grid)) return hipErrorInvalidValue;
+    return ladder_launch(launches, n_strip, [&] {
+        if (max_t <= 16) hipLaunchKernelGGL(lanczos_yuv_ladder<16>, dim3(strip_grid), dim3(64), strip_lds, stream, a);
+        else hipLaunchKernelGGL(lanczos_yuv_ladder<22>, dim3(strip_grid), dim3(64), strip_lds, stream, a);
+    }, n_tile, [&] { hipLaunchKernelGGL(lanczos_yuv_ladder_tile, dim3(tile_grid), dim3(256), tile_lds, stream, t); });
 }
 
 // (the pointer in chipvideo.cpp is constant-initialised to null, so the order of the units' initialisers does not matter)

@@ -11,8 +11,7 @@
 //   lanczos_rgb_ladder_tile   the rungs that take the tile route: 256-thread blocks, one per 32 x 4 or 8 x 4 output pixels.
 #include "lanczos_rgb_body.hip.h"
 #include "lanczos_rgb_ladder.h"
-
-#include <climits>
+#include "lanczos_ladder_launch.hip.h"
 
 namespace chv {
 
@@ -36,14 +35,6 @@ struct RgbLadderArgs {
 };
 static_assert(sizeof(RgbLadderArgs) <= 4096 - 256, "kernel arguments: 4 KB in all, 256 bytes of them the runtime's");
 
-// the rung whose range holds block b: first[] ascends, first[0] == 0
-CHV_DEV int rgb_rung_of(const RgbLadderArgs &a, int b) {
-    int r = 0;
-#pragma unroll
-    for (int k = 1; k < kLanczosPlanarLadderMaxRungs; k++) r = b >= a.first[k] ? k : r;
-    return r;
-}
-
 struct RgbBlock {
     RgbGeom g;
     DPlane dst, src;
@@ -56,20 +47,13 @@ struct RgbBlock {
 template <bool XCD>
 CHV_DEV RgbBlock rgb_decode(const RgbLadderArgs &a, int blk) {
     const uint64_t ka = (uint64_t)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-    const int r = rgb_rung_of(a, blk);
+    const int r = ladder_rung_of(a.first, blk);
     const RgbRung R = cld<RgbRung>(ka + offsetof(RgbLadderArgs, rung) + (uint64_t)r * sizeof(RgbRung));
     RgbBlock o;
-    const int b = blk - R.first_block;
-    int idx = b;
-    if (XCD) {
-        const int per_xcd = (R.total + 7) >> 3;
-        idx = (b & 7) * per_xcd + (b >> 3);
-        o.live = (b >> 3) < per_xcd && idx < R.total;
-    } else {
-        o.live = idx < R.total;
-    }
+    const LadderItem it = ladder_item<XCD>(blk - R.first_block, R.total);
+    o.live = it.live;
     if (!o.live) return o;
-    const int picture = idx / R.per_picture, rem = idx - picture * R.per_picture;
+    const int picture = it.idx / R.per_picture, rem = it.idx - picture * R.per_picture;
     o.by = rem / R.strips;
     o.bx = rem - o.by * R.strips;
     o.g = R.g;
@@ -98,24 +82,6 @@ __global__ __launch_bounds__(256) void lanczos_rgb_ladder_tile(const RgbLadderAr
     const RgbBlock blk = rgb_decode<false>(a, blockIdx.x);
     if (!blk.live) return;
     rgb_tile(blk.g, blk.dst, blk.src, blk.bx, blk.by, rgb_ladder_lsm);
-}
-
-// the records of one launch, largest range first; false when the grid would not fit 30 bits
-static bool rgb_ladder_order(RgbLadderArgs *a, const RgbRung *rungs, int n, int pad, unsigned *grid) {
-    int order[kLanczosPlanarLadderMaxRungs];
-    for (int k = 0; k < n; k++) order[k] = k;
-    std::stable_sort(order, order + n, [&](int x, int y) { return rungs[x].total > rungs[y].total; });
-    long first = 0;
-    for (int k = 0; k < kLanczosPlanarLadderMaxRungs; k++) a->first[k] = INT_MAX;
-    for (int k = 0; k < n; k++) {
-        a->rung[k] = rungs[order[k]];
-        a->rung[k].first_block = (int32_t)first;
-        a->first[k] = (int32_t)first;
-        first += ((long)a->rung[k].total + pad - 1) / pad * pad;
-        if (first > 0x3fffffff) return false;
-    }
-    *grid = (unsigned)first;
-    return true;
 }
 
 static hipError_t launch_lanczos_rgb_ladder(const LanczosRgbLadderJob &job, hipStream_t stream, int *launches) {
@@ -171,23 +137,12 @@ static hipError_t launch_lanczos_rgb_ladder(const LanczosRgbLadderJob &job, hipS
     a.batch = job.batch; a.per_image = job.n_rungs + 1; a.src_at = job.n_rungs; a.rows = rows;
     RgbLadderArgs t = a;
     unsigned strip_grid = 0, tile_grid = 0;
-    if (n_strip && !rgb_ladder_order(&a, strip, n_strip, 8, &strip_grid)) return hipErrorInvalidValue;
-    if (n_tile && !rgb_ladder_order(&t, tile, n_tile, 1, &tile_grid)) return hipErrorInvalidValue;
-    (void)hipGetLastError();
-    if (n_strip) {
+    if (n_strip && !ladder_order(&a, strip, n_strip, 8, &strip_grid)) return hipErrorInvalidValue;
+    if (n_tile && !ladder_order(&t, tile, n_tile, 1, &tile_grid)) return hipErrorInvalidValue;
+    return ladder_launch(launches, n_strip, [&] {
         if (tmax <= 12) hipLaunchKernelGGL(lanczos_rgb_ladder<12>, dim3(strip_grid), dim3(64), strip_lds, stream, a);
         else hipLaunchKernelGGL(lanczos_rgb_ladder<22>, dim3(strip_grid), dim3(64), strip_lds, stream, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ++*launches;
-    }
-    if (n_tile) {
-        hipLaunchKernelGGL(lanczos_rgb_ladder_tile, dim3(tile_grid), dim3(256), tile_lds, stream, t);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        ++*launches;
-    }
-    return hipSuccess;
+    }, n_tile, [&] { hipLaunchKernelGGL(lanczos_rgb_ladder_tile, dim3(tile_grid), dim3(256), tile_lds, stream, t); });
 }
 
 // (the pointer in chipvideo.cpp is constant-initialised to null, so the order of the units' initialisers does not matter)

@@ -10,10 +10,9 @@
 
 #include "device_types.h"
 #include "lanczos_planar.h"
+#include "lanczos_ladder_grid.h"      // kLanczosPlanarLadderMaxRungs
 
 namespace chv {
-
-constexpr int kLanczosPlanarLadderMaxRungs = 8;
 
 struct LanczosPlanarLadderRung {
     // per plane: the tables of (source plane's width, this rung's plane's width) and the same for the heights — device memory that stays
