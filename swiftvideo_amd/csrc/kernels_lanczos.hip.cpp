@@ -10,11 +10,9 @@
 //   C. vertical pass out of that array, packed BGRA store.
 // Both passes accumulate with one fused multiply-add per tap, taps in ascending order from
 // 0.0f — the same chain the oracle evaluates with fmaf().
-#include "pixel_math.hip.h"
+#include "lanczos_strip_parts.hip.h"
 
 #include <algorithm>
-#include <type_traits>
-#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -411,15 +409,11 @@ __global__ __launch_bounds__(64, CHV_LS_WAVES) void lanczos3_strip2(DPlane dst, 
 // the joins, and a prefetch register whose load is in flight must not be copied: tools/check_inflight.py); after each source
 // row a uniform test finishes the output rows whose last source row it was — their window starts at row (t + 1) % T.
 // Same chains, same bytes as lanczos3_bgra.
-template <typename F, int... Is>
-CHV_DEV bool lg_all_of(F &&f, std::integer_sequence<int, Is...>) { return (... && f(std::integral_constant<int, Is>{})); }
-template <int T> struct LgPre { static constexpr int value = T % 4 == 0 ? 4 : T % 3 == 0 ? 3 : 2; };      // prefetch depth: a divisor of T
-
 template <int T>
 __global__ __launch_bounds__(64, (T >= 14 ? 3 : 4)) void lanczos3_strip(DPlane dst, DPlane src, const int32_t *__restrict__ fx, const float *__restrict__ wx,
                                                                         const int32_t *__restrict__ fy, const float *__restrict__ wy, int rows_per_wave,
                                                                         int strips, int chunks, int total, int nv, const DPlane *__restrict__ batch) {
-    constexpr int PRE = LgPre<T>::value;
+    constexpr int PRE = LanczosPre<T>::value;
     const int b = blockIdx.x, per_xcd = (total + 7) >> 3;         // XCD-aware numbering, as in lanczos3_strip2
     const int idx = (b & 7) * per_xcd + (b >> 3);
     if ((b >> 3) >= per_xcd || idx >= total) return;
@@ -515,7 +509,7 @@ __global__ __launch_bounds__(64, (T >= 14 ? 3 : 4)) void lanczos3_strip(DPlane d
             }
             return true;
         };
-        lg_all_of(body, std::make_integer_sequence<int, T>{});
+        lanczos_all_of(body, std::make_integer_sequence<int, T>{});
     }
 #pragma unroll
     for (int p = 0; p < PRE; p++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pre[p]) :: "memory");

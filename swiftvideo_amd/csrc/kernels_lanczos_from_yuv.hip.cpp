@@ -154,7 +154,7 @@ static hipError_t launch_lanczos_from_yuv(const LanczosFromYuvJob &job, hipStrea
         g.fx = t.fx; g.wx = t.wx; g.fy = t.fy; g.wy = t.wy; g.tx = t.tx; g.ty = t.ty;
         g.dst = DPlane{ nullptr, d.w, d.h, 0, 1 };
         g.src = DPlane{ nullptr, job.src[p].w, job.src[p].h, 0, p && nv12 ? 2 : 1 };
-        if (g.dst.w < 1 || g.dst.h < 1 || g.src.w < 1 || g.src.h < 1 || planar_refuses(g.dst, g.src, t.tx, t.ty)) return hipErrorInvalidValue;
+        if (g.dst.w < 1 || g.dst.h < 1 || g.src.w < 1 || g.src.h < 1 || lanczos_refuses(g.dst.w, g.dst.h, g.src.w, g.src.h, t.tx, t.ty)) return hipErrorInvalidValue;
     }
     FromYuvArgs a{};
     a.batch = job.batch;

@@ -189,7 +189,7 @@ static hipError_t launch_lanczos_from_yuv_ladder(const LanczosFromYuvLadderJob &
             g.fx = t.fx; g.wx = t.wx; g.fy = t.fy; g.wy = t.wy; g.tx = t.tx; g.ty = t.ty;
             g.dst = DPlane{ nullptr, j.w, j.h, 0, 1 };
             g.src = DPlane{ nullptr, p ? job.chroma_w : job.luma_w, p ? job.chroma_h : job.luma_h, 0, p && nv12 ? 2 : 1 };
-            if (g.dst.w < 1 || g.dst.h < 1 || g.src.w < 1 || g.src.h < 1 || planar_refuses(g.dst, g.src, t.tx, t.ty)) return hipErrorInvalidValue;
+            if (g.dst.w < 1 || g.dst.h < 1 || g.src.w < 1 || g.src.h < 1 || lanczos_refuses(g.dst.w, g.dst.h, g.src.w, g.src.h, t.tx, t.ty)) return hipErrorInvalidValue;
         }
         FylPending P{};
         P.R.w = j.w; P.R.h = j.h; P.R.dst_at = r;

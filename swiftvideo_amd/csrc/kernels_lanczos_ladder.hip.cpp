@@ -97,7 +97,7 @@ static hipError_t launch_lanczos_ladder(const LanczosLadderJob &job, hipStream_t
     long work = 0;
     for (int r = 0; r < job.n_rungs; r++) {
         const LanczosLadderRung &j = job.rung[r];
-        if (j.w < 1 || j.h < 1 || to_yuv_refuses(j.w, j.h, job.src_w, job.src_h, j.tx, j.ty)) return hipErrorInvalidValue;
+        if (j.w < 1 || j.h < 1 || lanczos_refuses(j.w, j.h, job.src_w, job.src_h, j.tx, j.ty)) return hipErrorInvalidValue;
         LadderRung R{};
         R.fx = j.fx; R.wx = j.wx; R.fy = j.fy; R.wy = j.wy; R.tx = j.tx; R.ty = j.ty;
         R.dst_at = r * job.n_dst;

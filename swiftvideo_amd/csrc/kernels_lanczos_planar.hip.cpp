@@ -82,22 +82,22 @@ static hipError_t launch_lanczos_planar(const LanczosPlanarJob &job, hipStream_t
         const LanczosPlaneTables &t = job.tab[p];
         const DPlane &d = job.dst[p], &s = job.src[p];
         if (d.comps != s.comps || (d.comps != 1 && d.comps != 2)) return hipErrorInvalidValue;
-        if (planar_refuses(d, s, t.tx, t.ty)) return hipErrorInvalidValue;        // any plane refused: nothing is launched
+        if (lanczos_refuses(d.w, d.h, s.w, s.h, t.tx, t.ty)) return hipErrorInvalidValue;        // any plane refused: nothing is launched
         PlanarPlane &g = a.pl[p];
         g.fx = t.fx; g.wx = t.wx; g.fy = t.fy; g.wy = t.wy; g.tx = t.tx; g.ty = t.ty;
         g.dst = d; g.src = s;
     }
     int T = 0, nvmax = 0;
-    const bool strip_route = planar_strip_route(a.pl, job.n_planes, &T, &nvmax);      // (lanczos_planar_body.hip.h: the rule, shared with the ladder)
+    const bool strip_route = planar_strip_route(a.pl, job.n_planes, &T, &nvmax);      // (lanczos_route.h: the rule, shared with the ladder)
     (void)hipGetLastError();
     if (strip_route) {
-        a.rows = planar_strip_rows(planar_strip_work(a.pl, job.n_planes) * job.n_pictures);
+        a.rows = lanczos_strip_rows(planar_strip_work(a.pl, job.n_planes) * job.n_pictures, PS_MAX_ROWS);
         a.per_picture = planar_strip_blocks(a.pl, job.n_planes, a.rows);
         const long total = (long)a.per_picture * job.n_pictures;
         if (total > 0x3fffffff) return hipErrorInvalidValue;
         a.total = (int)total;
         dim3 grid((unsigned)(((a.total + 7) / 8) * 8));
-        const size_t lds = planar_wtab_bytes(a.rows, T) + (size_t)2 * nvmax * 16;       // the strip's vertical weights, the two-row staging ring
+        const size_t lds = lanczos_wtab_bytes(a.rows, T) + (size_t)2 * nvmax * 16;       // the strip's vertical weights, the two-row staging ring
         switch (T) {
         case 6: hipLaunchKernelGGL(planar_lanczos_strip<6>, grid, dim3(64), lds, stream, a); break;
         case 8: hipLaunchKernelGGL(planar_lanczos_strip<8>, grid, dim3(64), lds, stream, a); break;

@@ -97,14 +97,14 @@ static hipError_t launch_lanczos_rgb_ladder(const LanczosRgbLadderJob &job, hipS
     for (int r = 0; r < job.n_rungs; r++) {
         const LanczosRgbLadderRung &j = job.rung[r];
         const LanczosPlaneTables &t = j.tab;
-        if (j.w < 1 || j.h < 1 || t.tx < 1 || t.ty < 1 || rgb_refuses(j.w, j.h, job.src_w, job.src_h, t.tx, t.ty)) return hipErrorInvalidValue;
+        if (j.w < 1 || j.h < 1 || t.tx < 1 || t.ty < 1 || lanczos_refuses(j.w, j.h, job.src_w, job.src_h, t.tx, t.ty)) return hipErrorInvalidValue;
         RgbRung R{};
         R.g.fx = t.fx; R.g.wx = t.wx; R.g.fy = t.fy; R.g.wy = t.wy; R.g.tx = t.tx; R.g.ty = t.ty;
         R.dst_at = r;
         if (rgb_strip_route(j.w, job.src_w, t.tx, t.ty)) {
             R.strips = (j.w + 63) / 64;
             work += (long)R.strips * j.h * job.n_pictures;
-            R.g.T = rgb_strip_class(std::max(t.tx, t.ty));
+            R.g.T = lanczos_tap_class(std::max(t.tx, t.ty));
             tmax = std::max(tmax, R.g.T);
             strip_w[n_strip] = j.w; strip_h[n_strip] = j.h;
             strip[n_strip++] = R;
@@ -121,7 +121,7 @@ static hipError_t launch_lanczos_rgb_ladder(const LanczosRgbLadderJob &job, hipS
         }
     }
     // one count of rows per wave for the launch: the strip rungs share the chip.  A rung's ring is sized for its body's T.
-    const int rows = rgb_strip_rows(work);
+    const int rows = lanczos_strip_rows(work, RS_MAX_ROWS);
     size_t strip_lds = 0;
     for (int k = 0; k < n_strip; k++) {
         RgbRung &R = strip[k];
@@ -131,7 +131,7 @@ static hipError_t launch_lanczos_rgb_ladder(const LanczosRgbLadderJob &job, hipS
         const long total = (long)R.per_picture * job.n_pictures;
         if (total > 0x3fffffff) return hipErrorInvalidValue;
         R.total = (int32_t)total;
-        strip_lds = std::max(strip_lds, rgb_wtab_bytes(rows, R.g.T) + (size_t)2 * R.g.nv * 16);
+        strip_lds = std::max(strip_lds, lanczos_wtab_bytes(rows, R.g.T) + (size_t)2 * R.g.nv * 16);
     }
     RgbLadderArgs a{};
     a.batch = job.batch; a.per_image = job.n_rungs + 1; a.src_at = job.n_rungs; a.rows = rows;

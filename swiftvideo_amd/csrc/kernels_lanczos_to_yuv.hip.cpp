@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void lanczos_yuv_tile(const ToYuvArgs a) {
 static hipError_t launch_lanczos_to_yuv(const LanczosToYuvJob &job, hipStream_t stream) {
     if ((job.n_dst != 2 && job.n_dst != 3) || job.n_pictures < 1) return hipErrorInvalidValue;
     const DPlane &d = job.dst[0], &s = job.src;
-    if (to_yuv_refuses(d.w, d.h, s.w, s.h, job.tx, job.ty)) return hipErrorInvalidValue;          // nothing is launched
+    if (lanczos_refuses(d.w, d.h, s.w, s.h, job.tx, job.ty)) return hipErrorInvalidValue;          // nothing is launched
     ToYuvArgs a{};
     a.fx = job.fx; a.wx = job.wx; a.fy = job.fy; a.wy = job.wy; a.tx = job.tx; a.ty = job.ty;
     a.y = job.dst[0]; a.c0 = job.dst[1]; a.c1 = job.dst[job.n_dst == 3 ? 2 : 1]; a.src = s;

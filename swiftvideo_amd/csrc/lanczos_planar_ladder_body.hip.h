@@ -92,7 +92,7 @@ inline bool planar_ladder_plan(PlanarLadderPlan<Args> *L, const Args &proto, int
         for (int p = 0; p < np; p++) {
             PlanarPlane &g = P.pl[p];
             g = plane(r, p);
-            if (g.dst.w < 1 || g.dst.h < 1 || g.src.w < 1 || g.src.h < 1 || planar_refuses(g.dst, g.src, g.tx, g.ty)) return false;
+            if (g.dst.w < 1 || g.dst.h < 1 || g.src.w < 1 || g.src.h < 1 || lanczos_refuses(g.dst.w, g.dst.h, g.src.w, g.src.h, g.tx, g.ty)) return false;
         }
         P.R.dst_at = r * np;
         int T = 0, ring = 0;
@@ -115,14 +115,14 @@ inline bool planar_ladder_plan(PlanarLadderPlan<Args> *L, const Args &proto, int
     }
     // rows per wave from the whole launch's strip work (planar_lanczos_strip<T>'s rule over the sum): one count for every rung.  The strip
     // body finds its staging ring behind a weight table of ITS OWN tap class.
-    const int rows = planar_strip_rows(work);
+    const int rows = lanczos_strip_rows(work, PS_MAX_ROWS);
     for (int k = 0; k < L->n_strip; k++) {
         PlanarLadderPending &P = strip[k];
         P.R.per_picture = planar_strip_blocks(P.pl, np, rows);
         const long total = (long)P.R.per_picture * n_pictures;
         if (total > 0x3fffffff) return false;
         P.R.total = (int32_t)total;
-        L->strip_lds = std::max(L->strip_lds, planar_wtab_bytes(rows, P.R.T) + (size_t)2 * strip_ring[k] * 16);
+        L->strip_lds = std::max(L->strip_lds, lanczos_wtab_bytes(rows, P.R.T) + (size_t)2 * strip_ring[k] * 16);
     }
     L->strip = proto;
     L->strip.rows = rows;

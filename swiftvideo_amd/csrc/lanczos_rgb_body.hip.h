@@ -10,14 +10,12 @@
 //   rgb_tile       everything else: 256 threads per tile of tw x 4 output pixels (tw 32, or 8 where 32 columns of the rows a tile needs
 //                  would not fit 64 KB), horizontal pass from global memory into LDS, vertical pass out of it.  Simple on purpose.
 //
-// The host half — which route a geometry takes, its launch numbers, the refusal — is here too, so that the launcher does not restate it.
+// The host half — which route a geometry takes, its launch numbers — is here too, so that the launcher does not restate it.
 #pragma once
-#include "pixel_math.hip.h"
+#include "lanczos_strip_parts.hip.h"
+#include "lanczos_route.h"
 
 #include <algorithm>
-#include <cstddef>
-#include <type_traits>
-#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -35,11 +33,7 @@ struct RgbGeom {
     int32_t T;                        // strip route: the rung's own tap class (6 / 8 / 12 / 16 / 22 over its larger tap count)
 };
 
-template <typename F, int... Is>
-CHV_DEV bool rgb_all_of(F &&f, std::integer_sequence<int, Is...>) { return (... && f(std::integral_constant<int, Is>{})); }
 constexpr int RS_MAX_ROWS = 64;      // output rows per wave at most: their vertical weights live in LDS
-constexpr size_t rgb_wtab_bytes(int rows, int T) { return ((size_t)rows * T * sizeof(float) + 15) & ~(size_t)15; }
-template <int T> struct RgbPre { static constexpr int value = T % 4 == 0 ? 4 : T % 3 == 0 ? 3 : 2; };      // prefetch depth: a divisor of T
 
 // One strip: 64 output columns, rows [chunk * rows_per_wave, ...).  tx, ty <= T: the taps beyond tx read a staged texel with weight 0 in the
 // horizontal pass (fma(0, finite, acc) == acc; the chain starts at +0 and a sum with +0 in it is never -0), and the vertical pass walks the
@@ -47,12 +41,12 @@ template <int T> struct RgbPre { static constexpr int value = T % 4 == 0 ? 4 : T
 // loop runs over SOURCE rows, T per trip (lanczos3_strip<T> says why); an output row finishes at source row fy[j] + ty - 1.
 template <int T>
 CHV_DEV void rgb_strip(const RgbGeom &g, const DPlane &dst, const DPlane &src, int strip, int chunk, int rows_per_wave, uint8_t *lsm) {
-    constexpr int PRE = RgbPre<T>::value;
+    constexpr int PRE = LanczosPre<T>::value;
     const int32_t *__restrict__ fx = g.fx; const float *__restrict__ wx = g.wx;
     const int32_t *__restrict__ fy = g.fy; const float *__restrict__ wy = g.wy;
     const int tx = g.tx, ty = g.ty, nv = g.nv;
     float *wtab = (float *)lsm;                                   // [nrows][T]
-    chv_u32x4 *stage = (chv_u32x4 *)(lsm + rgb_wtab_bytes(rows_per_wave, T));      // [2][nv]
+    chv_u32x4 *stage = (chv_u32x4 *)(lsm + lanczos_wtab_bytes(rows_per_wave, T));      // [2][nv]
     const int lane = threadIdx.x;
     const int ox0 = strip * 64, j0 = chunk * rows_per_wave;
     if (ox0 >= dst.w || j0 >= dst.h) return;
@@ -80,21 +74,7 @@ CHV_DEV void rgb_strip(const RgbGeom &g, const DPlane &dst, const DPlane &src, i
         chv_u32x4 r = { pick(0), pick(1), pick(2), pick(3) };
         return r;
     };
-    const int pad = T - ty;                                       // window rows in front of a vertical filter's first tap
-    // The vertical weights of the strip's output rows, zero-padded in front to the window's T rows, go to LDS before the row loop (after it every
-    // wait for a global load would also wait for the row prefetch: one counter); the vertical chain reads a row of them at one address for all
-    // lanes.  (Through the scalar unit instead, 22 loads at computed offsets per output row: <22> spills SGPRs.)
-    for (int e0 = lane; e0 < nrows * T; e0 += 64 * 8) {           // (eight loads in flight per trip)
-        float wk[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int e = min(e0 + 64 * u, nrows * T - 1), j = e / T, k = e - j * T;
-            wk[u] = gld<float>(wy + (size_t)(j0 + j) * ty + max(k - pad, 0));
-            if (k < pad) wk[u] = 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) if (e0 + 64 * u < nrows * T) wtab[e0 + 64 * u] = wk[u];
-    }
+    lanczos_fill_wtab<T>(wtab, wy, ty, j0, nrows, lane);
     // (the load writes its destination registers some time AFTER the statement: the asm names the prefetch slot itself as its output, with
     // no temporary in between that the compiler could copy from before the data has landed; tools/check_inflight.py walks the object)
 #define RGB_ISSUE(SLOT, S) do { const int sy_ = min(max(row0 + (S), 0), src.h - 1); \
@@ -114,7 +94,6 @@ CHV_DEV void rgb_strip(const RgbGeom &g, const DPlane &dst, const DPlane &src, i
     const int S = cld<int32_t>((uint64_t)(uintptr_t)(fy + j0 + nrows - 1)) - row0 + ty;       // source rows this strip filters
     int jcur = 0, fcur = 0;                                       // next output row to finish, its first source row (fy[j0] - row0 = 0)
     for (int gi = 0; gi * T < S; gi++) {
-        // (expanded through a fold expression, not `#pragma unroll`: a window indexed at run time lives in scratch memory)
         auto body = [&](auto tc) -> bool {
             constexpr int t = decltype(tc)::value;
             const int s = gi * T + t;
@@ -164,7 +143,7 @@ CHV_DEV void rgb_strip(const RgbGeom &g, const DPlane &dst, const DPlane &src, i
             }
             return true;
         };
-        rgb_all_of(body, std::make_integer_sequence<int, T>{});
+        lanczos_all_of(body, std::make_integer_sequence<int, T>{});
     }
 #pragma unroll
     for (int p = 0; p < PRE; p++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pre[p]) :: "memory");      // (nothing leaves in flight)
@@ -250,15 +229,6 @@ CHV_DEV void rgb_tile(const RgbGeom &g, const DPlane &dst, const DPlane &src, in
 // ---------------------------------------------------------------------------------------------------------------------
 // The host half: one rung's route and launch numbers, from its geometry alone.
 
-// chv_scale_lanczos's refusal (launch_lanczos: the 8 x 4 tile's staged source beyond 160 KB), evaluated on the rung's sizes.  No geometry
-// of the strip route comes near it, so asking every rung is asking what the single call asks.
-inline bool rgb_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
-
 // vectors of one staged source row of a strip whose lanes read `taps` texels each: fx[x + 63] - fx[x] <= floor(63 scale) + 1, 3 texels of
 // alignment in front (launch_lanczos's formula)
 inline int rgb_row_vectors(int dw, int sw, int taps) {
@@ -272,16 +242,9 @@ inline bool rgb_strip_route(int dw, int sw, int tx, int ty) {
     return std::max(tx, ty) <= 22 && sw >= 4 && rgb_row_vectors(dw, sw, tx) <= 64;
 }
 
-// a strip rung's own body: the smallest tap class over its larger tap count (the padding costs (T - taps) / taps of the arithmetic).  The
-// KERNEL of a strip launch is <12> when no strip rung of it has a class above 12, else <22>; it is allocated the registers of its largest body.
-inline int rgb_strip_class(int tmax) { return tmax <= 6 ? 6 : tmax <= 8 ? 8 : tmax <= 12 ? 12 : tmax <= 16 ? 16 : 22; }
-
-// rows per wave from the launch's (strip, output row) pairs — lanczos3_strip<T>'s rule over the sum of the launch's rungs
-inline int rgb_strip_rows(long work) {
-    const long want = 4L * 1024 * 3;
-    const long r = (work + want - 1) / want;
-    return (int)std::min<long>(std::max<long>(r, 8), RS_MAX_ROWS);
-}
+// (a strip rung's own body is lanczos_tap_class of its larger tap count.  The KERNEL of a strip launch is <12> when no strip rung of it has a
+// class above 12, else <22>; it is allocated the registers of its largest body.  Rows per wave: lanczos_strip_rows over the sum of the
+// launch's rungs, at most RS_MAX_ROWS.)
 
 // tile route: the rows of the LDS array and the tile's width — 32 columns where that many float4 per row fit 64 KB, else 8, which the
 // refusal above bounds (max_rows * 8 * 16 <= 160 KB; with at most 256 taps max_rows <= 386, so 8 columns always fit 64 KB)

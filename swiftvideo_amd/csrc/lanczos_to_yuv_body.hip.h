@@ -7,13 +7,10 @@
 //
 // The host half — which route a geometry takes and with which launch numbers — is here as well, so that both units decide alike.
 #pragma once
-#include "pixel_math.hip.h"
-#include "device_types.h"
+#include "lanczos_strip_parts.hip.h"
+#include "lanczos_route.h"
 
 #include <algorithm>
-#include <cstddef>
-#include <type_traits>
-#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -81,10 +78,6 @@ CHV_DEV uint32_t yuv_chroma(const ToYuvMat &a, uint32_t s02, uint32_t s1) {
     return u | (v << 8);
 }
 
-template <typename F, int... Is>
-CHV_DEV bool ly_all_of(F &&f, std::integer_sequence<int, Is...>) { return (... && f(std::integral_constant<int, Is>{})); }
-template <int T> struct LyPre { static constexpr int value = T % 4 == 0 ? 4 : T % 3 == 0 ? 3 : 2; };      // prefetch depth: a divisor of T
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The strip body: one WAVE makes strip `strip` (64 output columns) x chunk `chunk` (`rows_per_wave` output rows, even) of picture P, T taps on
 // both axes, a staged row of `nv` vectors.  See lanczos3_strip<T> (kernels_lanczos.hip.cpp) for the structure: the loop runs over SOURCE rows, T
@@ -97,7 +90,7 @@ template <int T> struct LyPre { static constexpr int value = T % 4 == 0 ? 4 : T 
 // rows, same bytes.
 template <int T, bool TIGHT = false, typename A, typename G>
 CHV_DEV void lanczos_yuv_strip_body(const A &a, const ToYuvPlanes &P, const G &g, int chunk, int strip) {
-    constexpr int PRE = LyPre<T>::value;
+    constexpr int PRE = LanczosPre<T>::value;
     constexpr bool LEAN = T >= 18;                                // (scalar registers: see yuv_matrix)
     const DPlane dst = P.y, src = P.src;
     extern __shared__ __attribute__((aligned(16))) uint8_t ly_lsm[];
@@ -238,7 +231,7 @@ CHV_DEV void lanczos_yuv_strip_body(const A &a, const ToYuvPlanes &P, const G &g
             }
             return true;
         };
-        ly_all_of(body, std::make_integer_sequence<int, T>{});
+        lanczos_all_of(body, std::make_integer_sequence<int, T>{});
     }
 #pragma unroll
     for (int p = 0; p < PRE; p++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pre[p]) :: "memory");
@@ -318,13 +311,7 @@ CHV_DEV void lanczos_yuv_tile_body(const A &a, const ToYuvPlanes &P, const G &g,
 // ---------------------------------------------------------------------------------------------------------------------
 // The host half: the route of one geometry.
 
-// chv_scale_lanczos's refusal (launch_lanczos: the 8 x 4 tile's staged source beyond 160 KB) for the same geometry
-inline bool to_yuv_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
+// (the refusal is chv_scale_lanczos's for the same geometry: lanczos_refuses, lanczos_route.h)
 
 // The wave-per-strip kernel takes equal, even tap counts 6 .. 22 on both axes, a source of at least 4 texels and a staged row of at most 64
 // vectors: the vectors of that row, 0 for every other geometry (the tile kernel's).
@@ -337,11 +324,7 @@ inline int to_yuv_strip_vectors(int dw, int sw, int tx, int ty) {
 
 // rows per wave of the strip kernel for `work` = the launch's output rows x strips x pictures, as launch_lanczos chooses them — and even: a
 // chunk starts on an even output row, its chroma rows are its own
-inline int to_yuv_strip_rows(long work) {
-    const long want = 4L * 1024 * 3;
-    const long r = (work + want - 1) / want;
-    return ((int)std::min<long>(std::max<long>(r, 8), 256) + 1) & ~1;
-}
+inline int to_yuv_strip_rows(long work) { return (lanczos_strip_rows(work, 256) + 1) & ~1; }
 
 // the tile kernel: 32 x 4 pixels while the horizontally filtered rows of a tile fit 48 KB of LDS, 8 x 4 beyond (at most 256 taps and the
 // refusal above bound the 8-wide array by 37 KB).  Returns the dynamic LDS in bytes.

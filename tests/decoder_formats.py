@@ -109,7 +109,7 @@ def taps(n_in, n_out):
 
 
 def refuses(sw, sh, dw, dh):
-    """planar_refuses (lanczos_planar_body.hip.h): the 160 KB rule of chv_scale_lanczos on one image's own sizes"""
+    """lanczos_refuses (lanczos_route.h): the 160 KB rule of chv_scale_lanczos on one image's own sizes"""
     max_rows = int(3 * (sh / dh) + 2) + taps(sh, dh)
     max_cols = (int(7 * (sw / dw) + 2) + taps(sw, dw) + 3) & ~3
     return max_rows * 8 * 16 + max_rows * max_cols * 4 > 160 * 1024
@@ -131,7 +131,7 @@ def refused(sfmt, dfmt, iw, ih, ow, oh):
 
 
 def strip_route(sfmt, dfmt, iw, ih, ow, oh):
-    """x420_strip_route (lanczos_420_body.hip.h) with the source's own tap stride"""
+    """x420_strip_route (lanczos_route.h) with the source's own tap stride"""
     ims = images(sfmt, dfmt, iw, ih, ow, oh)
     tmax = max(max(taps(s[0], d[0]), taps(s[1], d[1])) for s, d, _, _ in ims)
     if tmax > 22:

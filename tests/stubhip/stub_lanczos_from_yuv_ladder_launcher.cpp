@@ -12,15 +12,9 @@
 #include <algorithm>
 
 #include "../../swiftvideo_amd/csrc/lanczos_from_yuv_ladder.h"
+#include "stub_lanczos_refuses.h"
 
 namespace chv {
-static bool stub_from_yuv_ladder_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
-
 static hipError_t stub_lanczos_from_yuv_ladder(const LanczosFromYuvLadderJob &job_in, hipStream_t stream, int *launches) {
     *launches = 0;
     const int snp = job_in.src_planes;
@@ -35,7 +29,7 @@ static hipError_t stub_lanczos_from_yuv_ladder(const LanczosFromYuvLadderJob &jo
         for (int p = 0; p < 2; p++) {
             const LanczosPlaneTables &t = p ? R.chroma : R.luma;
             const int sw = p ? job_in.chroma_w : job_in.luma_w, sh = p ? job_in.chroma_h : job_in.luma_h;
-            if (R.w < 1 || R.h < 1 || sw < 1 || sh < 1 || stub_from_yuv_ladder_refuses(R.w, R.h, sw, sh, t.tx, t.ty)) return hipErrorInvalidValue;
+            if (R.w < 1 || R.h < 1 || sw < 1 || sh < 1 || stub_lanczos_refuses(R.w, R.h, sw, sh, t.tx, t.ty)) return hipErrorInvalidValue;
             tmax = std::max(tmax, std::max(t.tx, t.ty));
         }
         route[tmax > 22] = true;

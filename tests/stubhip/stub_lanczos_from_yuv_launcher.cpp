@@ -9,15 +9,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../swiftvideo_amd/csrc/lanczos_from_yuv.h"
+#include "stub_lanczos_refuses.h"
 
 namespace chv {
-static bool stub_from_yuv_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
-
 static hipError_t stub_lanczos_from_yuv(const LanczosFromYuvJob &job_in, hipStream_t stream) {
     const int snp = job_in.src_planes;
     if ((snp != 2 && snp != 3) || job_in.n_pictures < 1 || (job_in.n_pictures > 1 && !job_in.batch)) return hipErrorInvalidValue;
@@ -26,7 +20,7 @@ static hipError_t stub_lanczos_from_yuv(const LanczosFromYuvJob &job_in, hipStre
     for (int p = 0; p < 2; p++) {
         const LanczosPlaneTables &t = p ? job_in.chroma : job_in.luma;
         const DPlane &s = job_in.src[p];
-        if (job_in.dst.w < 1 || job_in.dst.h < 1 || s.w < 1 || s.h < 1 || stub_from_yuv_refuses(job_in.dst.w, job_in.dst.h, s.w, s.h, t.tx, t.ty))
+        if (job_in.dst.w < 1 || job_in.dst.h < 1 || s.w < 1 || s.h < 1 || stub_lanczos_refuses(job_in.dst.w, job_in.dst.h, s.w, s.h, t.tx, t.ty))
             return hipErrorInvalidValue;
     }
     if (stubhip_launch_should_fail()) return hipErrorLaunchFailure;

@@ -10,15 +10,9 @@
 #include <vector>
 
 #include "../../swiftvideo_amd/csrc/lanczos_ladder.h"
+#include "stub_lanczos_refuses.h"
 
 namespace chv {
-static bool stub_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
-
 static hipError_t stub_lanczos_ladder(const LanczosLadderJob &job_in, hipStream_t stream, int *launches) {
     *launches = 0;
     if ((job_in.n_dst != 2 && job_in.n_dst != 3) || job_in.n_pictures < 1 || job_in.n_rungs < 1 || job_in.n_rungs > kLanczosLadderMaxRungs || !job_in.batch)
@@ -28,7 +22,7 @@ static hipError_t stub_lanczos_ladder(const LanczosLadderJob &job_in, hipStream_
     std::vector<int> route[2];
     for (int r = 0; r < job_in.n_rungs; r++) {
         const LanczosLadderRung &g = job_in.rung[r];
-        if (stub_refuses(g.w, g.h, job_in.src_w, job_in.src_h, g.tx, g.ty)) return hipErrorInvalidValue;
+        if (stub_lanczos_refuses(g.w, g.h, job_in.src_w, job_in.src_h, g.tx, g.ty)) return hipErrorInvalidValue;
         route[g.tx == g.ty && g.tx >= 6 && g.tx <= 22 && (g.tx & 1) == 0 ? 0 : 1].push_back(r);
     }
     const LanczosLadderJob job = job_in;

@@ -12,14 +12,9 @@
 #include <algorithm>
 
 #include "../../swiftvideo_amd/csrc/lanczos_rgb_ladder.h"
+#include "stub_lanczos_refuses.h"
 
 namespace chv {
-static bool stub_rgb_ladder_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
 static bool stub_rgb_ladder_tile(const LanczosRgbLadderJob &job, const LanczosRgbLadderRung &R) {
     const int nv = ((int)(63 * ((double)job.src_w / (double)R.w)) + 1 + 3 + R.tab.tx + 3) / 4 + 1;
     return !(std::max(R.tab.tx, R.tab.ty) <= 22 && job.src_w >= 4 && nv <= 64);
@@ -31,7 +26,7 @@ static hipError_t stub_lanczos_rgb_ladder(const LanczosRgbLadderJob &job_in, hip
     bool route[2] = { false, false };
     for (int r = 0; r < job_in.n_rungs; r++) {
         const LanczosRgbLadderRung &R = job_in.rung[r];
-        if (R.w < 1 || R.h < 1 || job_in.src_w < 1 || job_in.src_h < 1 || stub_rgb_ladder_refuses(R.w, R.h, job_in.src_w, job_in.src_h, R.tab.tx, R.tab.ty))
+        if (R.w < 1 || R.h < 1 || job_in.src_w < 1 || job_in.src_h < 1 || stub_lanczos_refuses(R.w, R.h, job_in.src_w, job_in.src_h, R.tab.tx, R.tab.ty))
             return hipErrorInvalidValue;
         route[stub_rgb_ladder_tile(job_in, R)] = true;
     }

@@ -12,15 +12,9 @@
 #include <vector>
 
 #include "../../swiftvideo_amd/csrc/lanczos_to_420.h"
+#include "stub_lanczos_refuses.h"
 
 namespace chv {
-static bool stub_to_420_refuses(int dw, int dh, int sw, int sh, int tx, int ty) {
-    const double sy = (double)sh / (double)dh, sx = (double)sw / (double)dw;
-    const int max_rows = (int)(3 * sy + 2) + ty;
-    const int max_cols = ((int)(7 * sx + 2) + tx + 3) & ~3;
-    return (size_t)max_rows * 8 * 16 + (size_t)max_rows * max_cols * 4 > 160 * 1024;
-}
-
 static hipError_t stub_lanczos_to_420(const LanczosTo420Job &job_in, hipStream_t stream, int *launches) {
     *launches = 0;
     const int np = job_in.dst_planes, snp = job_in.src_planes;
@@ -33,7 +27,7 @@ static hipError_t stub_lanczos_to_420(const LanczosTo420Job &job_in, hipStream_t
         bool strip = true;
         for (int p = 0; p < np; p++) {
             const int sw = p ? job_in.chroma_w : job_in.luma_w, sh = p ? job_in.chroma_h : job_in.luma_h;
-            if (g.w[p] < 1 || g.h[p] < 1 || sw < 1 || sh < 1 || stub_to_420_refuses(g.w[p], g.h[p], sw, sh, g.tab[p].tx, g.tab[p].ty)) return hipErrorInvalidValue;
+            if (g.w[p] < 1 || g.h[p] < 1 || sw < 1 || sh < 1 || stub_lanczos_refuses(g.w[p], g.h[p], sw, sh, g.tab[p].tx, g.tab[p].ty)) return hipErrorInvalidValue;
             if (g.tab[p].tx > 22 || g.tab[p].ty > 22) strip = false;
         }
         route[strip ? 0 : 1].push_back(r);

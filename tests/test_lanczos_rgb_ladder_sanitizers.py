@@ -23,7 +23,7 @@ def _build(kind):
     exe = OUT / f"lanczos_rgb_ladder_stress_{kind}"
     srcs = [CSRC / "chipvideo.cpp", CSRC / "geom_store.cpp", CSRC / "lanczos_from_yuv.h", CSRC / "lanczos_from_yuv_ladder.h", CSRC / "lanczos_rgb_ladder.h", CSRC / "lanczos_420.h", CSRC / "lanczos_planar_ladder.h", CSRC / "lanczos_ladder_grid.h",
             CSRC / "lanczos_ladder.h", CSRC / "lanczos_to_yuv.h", CSRC / "lanczos_planar.h", CSRC / "rebind.h", CSRC / "device_types.h", CSRC / "geom_cache.h",
-            CSRC / "switches.h", ROOT / "include" / "chipvideo.h", STUB / "stub_runtime.cpp", STUB / "stub_launchers.cpp",
+            CSRC / "switches.h", ROOT / "include" / "chipvideo.h", STUB / "stub_runtime.cpp", STUB / "stub_lanczos_refuses.h", STUB / "stub_launchers.cpp",
             STUB / "stub_lanczos_rgb_ladder_launcher.cpp", STUB / "lanczos_rgb_ladder_stress.cpp", STUB / "hip" / "hip_runtime.h", STUB / "build_lanczos.sh"]
     if not exe.exists() or exe.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
         subprocess.check_call(["bash", str(STUB / "build_lanczos.sh"), "rgb_ladder", kind, str(exe)])
