@@ -24,6 +24,7 @@
 
 #include "device_types.h"
 #include "switches.h"
+#include "tick_route.h"
 #include "geom_cache.h"
 #include "rebind.h"
 #include "lanczos_planar.h"
@@ -49,15 +50,7 @@ hipError_t launch_selftest(float *out_f, const float *in_f, uint8_t *out_c, cons
 hipError_t launch_selftest_pack(const int *b, const int *g, const int *r, uint32_t *out, int n, hipStream_t stream);
 hipError_t launch_selftest_pack_codes(const float *in, uint32_t *out, int n, hipStream_t stream);
 hipError_t launch_selftest_matrices(int dir, int csc, uint32_t *out, uint32_t *mism, hipStream_t stream);
-// kernels_fast.hip.cpp
-const char *fast_path_name(int path);
-bool wave_layers_by_value(int target_format, const DTick *tick_host, const DLayer *layers_host);      // kernels_wave_yuv.hip.cpp
-bool fast_path_is_wave(int path);                // the strip kernels (they take per-layer geometry tables: geom_cache.h)
-bool fast_path_by_value(int path);
-int split_stream_prefix(const DTick *ticks, const DLayer *layers, int n_ticks);      // kernels_fast.hip.cpp
-int fast_path_stream_bgra();
-int select_tail_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks);      // a lone tick's descriptors can travel as kernel arguments (ticks == layers == nullptr)
-int select_fast_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks, bool transient = false);   // transient: one tick, launched once
+// kernels_fast.hip.cpp (the routes it launches: tick_route.h)
 // tables: the launch's geometry tables for the strip kernels (geom_cache.h; nullptr: none — they compute their geometry in place)
 hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *layers_host,
                             const DTick *ticks, const DLayer *layers, int n_ticks,

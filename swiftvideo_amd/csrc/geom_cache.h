@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
+#include "tick_route.h"
 
 // 1: layers of a batch take their per-strip geometry from the batch's tables (WaveStrip::setup_cached); 0: always computed in place
 #ifndef CHV_GEOM_CACHE
@@ -23,7 +24,7 @@
 
 namespace chv {
 
-constexpr int WTW = 64;                 // strip width: one lane per column
+// (WTW, the strip width: tick_route.h)
 
 // ---- a table's layout (one per geometry class: same matrices, source plane sizes, canvas size) ----------------------------------------------
 // [GeomHdr][flag word per strip, row-major, padded to 16 bytes][GeomCol per strip column][row record (row_bytes) per strip row].  The host lays
@@ -48,14 +49,7 @@ inline void geom_set_table(DLayer &L, const void *table) {
 }
 inline void *geom_table(const DLayer &L) { return (void *)(uintptr_t)(((uint64_t)(uint32_t)L.pad2[1] << 32) | (uint64_t)(uint32_t)L.pad2[0]); }
 
-// what the tables were built for: any difference rebuilds them (strip height and LDS layout are chosen per LAUNCH, launch_wave_layers)
-struct GeomConfig {
-    int32_t target_format, wth, p0pitch, p0rows, p1pitch, p1rows, planar_any, strips_x, strips_y, n_layers;
-    bool operator==(const GeomConfig &o) const {
-        return target_format == o.target_format && wth == o.wth && p0pitch == o.p0pitch && p0rows == o.p0rows && p1pitch == o.p1pitch && p1rows == o.p1rows &&
-               planar_any == o.planar_any && strips_x == o.strips_x && strips_y == o.strips_y && n_layers == o.n_layers;
-    }
-};
+// (GeomConfig, what the tables were built for, and wave_geom_config, which answers it for a launch: tick_route.h)
 
 // The tables of one launch's layers, handed to the strip kernels' launcher (launch_tick_fast -> launch_wave_layers): a batch's (chv_batch), the
 // temporary one of a lone tick that builds, or the answer the store gave a lone tick before its layers travelled (built + patched, no layer arrays).
@@ -105,9 +99,6 @@ bool geom_store_patch(int target_format, const DTick *ticks_host, DLayer *layers
 uint64_t geom_store_counter(int which);
 
 // ---- what the strip kernels' translation unit gives the store (kernels_wave_yuv.hip.cpp) ----
-// the configuration launch_wave_layers will launch these ticks with; false: a launch that takes no tables (RGB layers only, or nothing staged)
-bool wave_geom_config(int target_format, const DTick *ticks_host, const DLayer *layers_host, int n_ticks, int maxW, int maxH, int n_layers_total,
-                      GeomConfig *cfg);
 // geom_precompute over `blocks` (class, strip) pairs of the job list in device memory (reports through hipGetLastError)
 hipError_t launch_geom_precompute(const GeomConfig &cfg, const GeomJob *jobs, int n_jobs, int blocks, hipStream_t stream);
 

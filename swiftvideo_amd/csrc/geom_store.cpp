@@ -1,7 +1,8 @@
 // geom_store.cpp — the host side of the strip kernels' geometry tables (geom_cache.h): a launch's tables built, given to the device's store and
-// found there, the layers pointed at them.  Of the kernels' translation unit it takes two things (kernels_wave_yuv.hip.cpp): the launch
-// configuration (wave_geom_config) and the launch of the kernel that fills the tables (launch_geom_precompute).
+// found there, the layers pointed at them.  The launch configuration comes from the route unit (tick_route.cpp: wave_geom_config); of the kernels'
+// translation unit it takes one thing (kernels_wave_yuv.hip.cpp): the launch of the kernel that fills the tables (launch_geom_precompute).
 #include "geom_cache.h"
+#include "tick_route.h"
 #include "switches.h"
 
 #include <atomic>

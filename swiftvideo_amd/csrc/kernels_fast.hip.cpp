@@ -23,8 +23,8 @@
 // Every path here produces exactly the bytes of kernels_general.hip.cpp; the host
 // picks a path per batch (select_fast_path) and falls back to the general kernel.
 #include "tile_common.hip.h"
+#include "tick_route.h"
 #include "switches.h"
-#include <vector>
 
 #include <algorithm>
 #include <cmath>
@@ -34,40 +34,24 @@
 
 namespace chv {
 
-enum FastPath : int { FP_NONE = -1, FP_NV12_BGRA_TILED = 0, FP_Y420P_BGRA_TILED = 1, FP_WAVE_LAYERS = 2, FP_WAVE_NV12 = 3, FP_WAVE_Y420P = 4, FP_STREAM = 5, FP_CLEAR_BGRA = 6, FP_STREAM_NV12 = 7, FP_STREAM_Y420P = 8, FP_COUNT };
+using namespace fast_path_ids;       // (tick_route.h)
 
-// kernels_wave.hip.cpp / kernels_wave_yuv.hip.cpp
-bool wave_layers_eligible(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks, bool tail = false);
 // kernels_stream.hip.cpp
-bool bgra_stream_eligible(const DTick *ticks, const DLayer *layers, int n_ticks);
 hipError_t launch_bgra_stream(const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int maxW, int maxH, hipStream_t stream);
-bool yuv_stream_eligible(int tf, const DTick *ticks, const DLayer *layers, int n_ticks, bool transient);
 hipError_t launch_yuv_stream(int tf, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int maxW, int maxH, hipStream_t stream);
 // (tables: the launch's geometry tables, geom_cache.h; nullptr: none)
 struct GeomCache;
 hipError_t launch_wave_layers(int target_format, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers,
                               int n_ticks, int maxW, int maxH, hipStream_t stream, GeomCache *tables);
 
-#ifndef CHV_TW
-#define CHV_TW 128
-#endif
-constexpr int TW = CHV_TW;       // tile width  (output pixels), a multiple of 64
+// (TW, the tile width, KT, the tiles per block, and the tile heights TH_SMALL / TH_LARGE: tick_route.h)
 #ifndef CHV_PXT
 #define CHV_PXT 2
 #endif
 constexpr int PXT = CHV_PXT;     // horizontally adjacent pixels per thread (4: one 16-byte store, 2: one 8-byte store)
 constexpr int TXT = TW / PXT;    // threads across a tile row
 constexpr int TYT = NTHREADS / TXT;   // tile rows covered per pass
-// Tile height (output rows) is a kernel template parameter THV: 32 rows for launches that fill the chip anyway (more pixels
-// per barrier interval: -6 % on cfg2), 16 rows for small launches such as a single mixer tick (twice the blocks: 9.6 instead
-// of 12.3 us for one 720p tick).  RPT = THV / TYT rows per thread.
-constexpr int TH_SMALL = 16, TH_LARGE = 32;
 // NTHREADS = 256: 32 x 8 threads, each 4 px x 2 rows per tile
-
-#ifndef CHV_KT
-#define CHV_KT 4
-#endif
-constexpr int KT = CHV_KT;             // tiles per block: a vertical strip of KT tiles shares its column tables
 
 // Per-strip tables, structure-of-arrays so that lane-adjacent reads are conflict free.
 // Tap positions are the UNCLAMPED i0 = floor(u - 0.5) of the linear filter (tap 1 is
@@ -86,6 +70,8 @@ struct TileTablesT {
     int csum[TW / 64][8];          // per column wave
     int rsum[KT][8];               // per tile of the strip
 };
+static_assert(sizeof(TileTablesT<TH_SMALL>) == tile_tables_bytes(TH_SMALL) && sizeof(TileTablesT<TH_LARGE>) == tile_tables_bytes(TH_LARGE),
+              "tick_route.h: tile_dims sizes the LDS with tile_tables_bytes");
 
 // axis_entry_x / axis_entry_y, blend_bgra_general and the LDS / global YUV samplers live in tile_common.hip.h
 // (shared with the wave kernels)
@@ -389,38 +375,8 @@ __global__ __launch_bounds__(NTHREADS, CHV_MINW) void tick_yuv_bgra_tiled_one(co
 }
 
 // ---------------------------------------------------------------------------
-// host side: path selection and launch geometry
+// host side: launch geometry (which launch takes this kernel, and tile_dims: tick_route.cpp)
 // ---------------------------------------------------------------------------
-struct TileDims { int ypitch, yrows, cpitch, crows; size_t lds; };
-static size_t tables_bytes(int th) { return th == TH_LARGE ? sizeof(TileTablesT<TH_LARGE>) : sizeof(TileTablesT<TH_SMALL>); }
-
-static bool finite16(const float *m) {
-    for (int i = 0; i < 16; i++) if (!(m[i] - m[i] == 0.f)) return false;
-    return true;
-}
-
-// LDS rectangle one tile of this layer can touch, from the layer's scale factors.
-static TileDims tile_dims(const DTick &T, const DLayer &L, int TH) {
-    const float *U = L.u;
-    // |d(uv)/d(pixel)| as a fraction of the source per output pixel
-    double sxr = std::fabs((double)U[U_TEXTURE + 0] * (double)U[U_TRANSFORM + 0] * 2.0 / (double)T.W);
-    double syr = std::fabs((double)U[U_TEXTURE + 5] * (double)U[U_TRANSFORM + 5] * 2.0 / (double)T.H);
-    TileDims d;
-    int yspan = (int)std::ceil(TW * sxr * L.src.pl[0].w) + 4;   // texels incl. tap 1 and rounding slack
-    int cspan = (int)std::ceil(TW * sxr * L.src.pl[1].w) + 4;
-    d.ypitch = ((yspan + 15) / 16 + 3) * 16;                    // luma bytes: vectors + alignment + 2 pad vectors
-    const bool planar = L.kind == LK_BGRA_FROM_Y420P;
-    d.cpitch = planar ? ((cspan + 15) / 16 + 3) * 16 : ((cspan + 7) / 8 + 3) * 16;   // chroma bytes: U and V tiles (planar) / (u, v) pairs (NV12)
-    // rows a tile's taps span: <= ceil((TH-1)*scale) + 2 (tap 1 of the last row) <= ceil(TH*scale) + 2
-    d.yrows = (int)std::ceil(TH * syr * L.src.pl[0].h) + 3;
-    d.crows = (int)std::ceil(TH * syr * L.src.pl[1].h) + 3;
-    d.lds = tables_bytes(TH) + (size_t)d.ypitch * d.yrows + (size_t)d.cpitch * d.crows * (planar ? 2 : 1);
-    return d;
-}
-
-// what the staged loads need: 16-byte aligned base and pitch, rows of at least one 16-byte vector
-static bool aligned16(const DPlane &p) { return (((uintptr_t)p.ptr) & 15) == 0 && (p.pitch & 15) == 0 && p.w * p.comps >= 16; }
-
 // img_clear_bgra on its own (the first launch of an unchanged mix.video.swift tick): every canvas pixel becomes (0, 0, 0, 1).  The plane
 // travels by value — a transient launch, no descriptor copy in front of it.
 __global__ __launch_bounds__(256) void canvas_clear_bgra(const DPlane D, int W, int H) {
@@ -434,136 +390,6 @@ __global__ __launch_bounds__(256) void canvas_clear_bgra(const DPlane D, int W, 
         for (int i = x; i < min(x + 4, w); i++) *(uint32_t *)(row + (size_t)i * 4) = 0xFF000000u;
     }
 }
-
-const char *fast_path_name(int path) {
-    switch (path) {
-    case FP_NV12_BGRA_TILED: return "tick_nv12_bgra_tiled";
-    case FP_Y420P_BGRA_TILED: return "tick_y420p_bgra_tiled";
-    case FP_WAVE_LAYERS: return "tick_bgra_wave";
-    case FP_STREAM: return "tick_bgra_stream";
-    case FP_CLEAR_BGRA: return "canvas_clear_bgra";
-    case FP_WAVE_NV12: return "tick_yuv_wave<nv12>";
-    case FP_WAVE_Y420P: return "tick_yuv_wave<y420p>";
-    case FP_STREAM_NV12: return "tick_yuv_stream<nv12>";
-    case FP_STREAM_Y420P: return "tick_yuv_stream<y420p>";
-    default: return "none";
-    }
-}
-
-// the single-purpose kernel: exactly one YUV layer per tick (cfg2 / cfg4): block-tiled, strips of four tiles with the next
-// tile's rectangle prefetched — 0.40-0.46 ms per 256 cfg2 ticks against 0.78 for the wave-per-strip kernel.  (RGB-only ticks
-// had a block-tiled kernel of their own until the wave kernel overtook it: cfg3 1.92 vs 2.23 ms, cfg5 3.36 vs 3.67.)
-static int select_single_purpose(const DTick *ticks, const DLayer *layers, int n_ticks) {
-    for (int i = 0; i < n_ticks; i++) {
-        const DTick &T = ticks[i];
-        if (T.n_layers != 1 || T.clear_first != ticks[0].clear_first) return FP_NONE;
-        const DLayer &L = layers[T.first_layer];
-        if ((L.kind != LK_BGRA_FROM_NV12 && L.kind != LK_BGRA_FROM_Y420P) || !(L.flags & LF_AXIS_ALIGNED)) return FP_NONE;
-        if (L.kind != layers[ticks[0].first_layer].kind) return FP_NONE;
-        if (!csc_absorbable(L.csc) && switches().bgra_path.load(std::memory_order_relaxed) != 2) return FP_NONE;      // (its fast rows need the absorbed matrix: the strip kernel is the faster one there)
-        if (L.kind == LK_BGRA_FROM_Y420P && !aligned16(L.src.pl[2])) return FP_NONE;
-        if (!finite16(L.u + U_TRANSFORM) || !finite16(L.u + U_TEXTURE) || !finite16(L.u + U_BORDER)) return FP_NONE;
-        if (!aligned16(T.dst.pl[0]) || !aligned16(L.src.pl[0]) || !aligned16(L.src.pl[1])) return FP_NONE;
-        if (tile_dims(T, L, TH_SMALL).lds > (size_t)LDS_BUDGET) return FP_NONE;
-    }
-    return layers[ticks[0].first_layer].kind == LK_BGRA_FROM_Y420P ? FP_Y420P_BGRA_TILED : FP_NV12_BGRA_TILED;
-}
-
-int select_fast_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks, bool transient) {
-    if (n_ticks <= 0) return FP_NONE;
-    // A/B switches for measurements and tests (switches.h: environment read once, chv_debug_set_switch afterwards):
-    //   force_general (CHV_FORCE_GENERAL=1)  everything through the general kernels
-    //   bgra_path (CHV_BGRA_PATH=wave)       BGRA canvases: the wave-per-strip kernel also where the single-purpose kernel (exactly
-    //                                        one YUV layer per tick) would be chosen;  =tiled: the single-purpose kernel wherever it applies
-    const int bp = switches().bgra_path.load(std::memory_order_relaxed);
-    if (switches().force_general.load(std::memory_order_relaxed)) return FP_NONE;
-    // 4:2:0 canvases (the reference's own kernels): one wave per strip, or the general quad kernel
-    // 4:2:0 canvases: cleared ticks of 1..4 axis-aligned layers without fill paint can stream their source rows (kernels_stream_yuv.hip.cpp: rows
-    // outermost, a ring per layer, launches of every size); by default where that measured faster, everything else keeps the strip kernel
-    if (target_format != TF_BGRA) {
-        // Lone ticks of video layers from 720p up go to the strip kernel since ITS descriptors travel as a kernel argument too (WaveOne): 19.3 /
-        // 20.3 / 30.6 us per 720p / 1080p / 2160p tick with the host wait against 20.5 / 22.5 / 35.7 through the rings; at 360p the streaming
-        // kernel's short chunks keep it ahead (17.8 against 19.0), and the encoder side's integer frames are level (profiles/r06_notes.md section 15).
-        // (Asked before the streaming kernel's own, longer list of conditions: where the strips can take such a tick they do either way.)
-        if (transient && n_ticks == 1 && switches().yuv_stream.load(std::memory_order_relaxed) == 1 && (long)ticks[0].W * ticks[0].H >= 500000 &&
-            ticks[0].n_layers >= 1 && ticks[0].n_layers <= WAVE_ONE_LAYERS && ticks[0].clear_first) {
-            bool video_only = true;
-            for (int l = 0; l < ticks[0].n_layers; l++) {
-                const int k = layers[ticks[0].first_layer + l].kind;
-                video_only = video_only && (k == LK_YUV_FROM_NV12 || k == LK_YUV_FROM_Y420P);
-            }
-            if (video_only && wave_layers_eligible(target_format, ticks, layers, n_ticks)) return target_format == TF_NV12 ? FP_WAVE_NV12 : FP_WAVE_Y420P;
-        }
-        if (yuv_stream_eligible(target_format, ticks, layers, n_ticks, transient)) return target_format == TF_NV12 ? FP_STREAM_NV12 : FP_STREAM_Y420P;
-    }
-    if (target_format != TF_BGRA)
-        return wave_layers_eligible(target_format, ticks, layers, n_ticks) ? (target_format == TF_NV12 ? FP_WAVE_NV12 : FP_WAVE_Y420P) : FP_NONE;
-    // ticks of 2..4 full-frame NV12 layers of one geometry on a cleared canvas: rows outermost, layers innermost (kernels_stream.hip.cpp);
-    // one-layer ticks: a transient launch (chv_composite / chv_run_kernel: 19.7 against 22.6 us with the host wait through the tiled kernel —
-    // its descriptors travel as kernel arguments, tools/tick_rows_sweep.sh; a one-tick BATCH reads them through pointers and is level with
-    // the tiled kernel, which keeps it), otherwise on request (CHV_BGRA_PATH=stream; cfg2's 256-tick launches: 0.55 against 0.44 ms).
-    // Launches of every size: the streaming kernel takes its chunk height as an
-    // argument, and with 4-row chunks a lone 720p tick is 10.9 us on the chip against ~17 through 8-row strips of the strip kernel
-    // (26.4 against 33.7 us per tick with the host wait; tools/tick_rows_sweep.sh, tools/stream_threshold_sweep.sh).
-    if (transient && n_ticks == 1 && ticks[0].n_layers == 0 && ticks[0].clear_first && (((uintptr_t)ticks[0].dst.pl[0].ptr) & 3) == 0 &&
-        (ticks[0].dst.pl[0].pitch & 3) == 0)
-        return FP_CLEAR_BGRA;
-    // A lone tick of ONE NV12 layer on a cleared canvas, now that the strip kernel has a twin that takes such a tick as a kernel argument
-    // (tick_bgra_wave_one): the strips are ahead of the streaming kernel's twin on canvases from ~1.4 Mpixel up (a 1080p canvas: 20.8 against
-    // 23.2 us with the host wait; at 720p the streaming kernel keeps it, 19.4 against 21.3) and of the tiled kernel's twin wherever the
-    // streaming kernel does not apply (a picture-in-picture inset: 22.5 against 24.1 us at 720p, 21.2 against 23.4 at 1080p) —
-    // tools/lone_bgra_routes.py.  Planar sources stay (their strip instantiation has no twin).
-    const bool lone_nv12 = transient && bp == 0 && n_ticks == 1 && ticks[0].n_layers == 1 && ticks[0].clear_first &&
-                           (layers[ticks[0].first_layer].kind == LK_BGRA_FROM_NV12 || layers[ticks[0].first_layer].kind == LK_BGRA_FROM_Y420P);
-    if ((bp == 0 || bp == 3) && bgra_stream_eligible(ticks, layers, n_ticks)) {
-        if (lone_nv12 && (long)ticks[0].W * ticks[0].H >= 1400000 && wave_layers_eligible(TF_BGRA, ticks, layers, n_ticks)) return FP_WAVE_LAYERS;
-        if (bp == 3 || ticks[0].n_layers >= 2 || transient) return FP_STREAM;
-    } else if (lone_nv12 && wave_layers_eligible(TF_BGRA, ticks, layers, n_ticks)) return FP_WAVE_LAYERS;
-    if (bp != 1) {
-        int p = select_single_purpose(ticks, layers, n_ticks);
-        // planar sources in launches that fill the chip: the y420p-only instantiation of the wave kernel is the faster one
-        // (cfg2_y420p 0.574 -> 0.532 ms; NV12 stays: 0.467 tiled vs 0.487 wave); small launches keep the tiled kernel's short strips
-        if (p == FP_Y420P_BGRA_TILED && bp != 2) {
-            long strips = 0;
-            for (int i = 0; i < n_ticks; i++) strips += (long)((ticks[i].W + 63) / 64) * ((ticks[i].H + 15) / 16);
-            if (strips >= 8192 && wave_layers_eligible(TF_BGRA, ticks, layers, n_ticks)) return FP_WAVE_LAYERS;
-        }
-        if (p != FP_NONE) return p;
-    }
-    // any mix of NV12 / y420p / BGRA / RGBA layers, any number of them.  (Launches that do not clear take the strip kernel also when ALL their
-    // layers need its per-pixel path — rotated overlays added to composed canvases —: its grid covers the layers' boxes only, and measured
-    // against the general kernel on the same boxes it is the faster one, 81 against 96 us for pipeline_logo's 128 rotated 320 x 180 logos.)
-    return wave_layers_eligible(TF_BGRA, ticks, layers, n_ticks, !ticks[0].clear_first) ? FP_WAVE_LAYERS : FP_NONE;
-}
-
-// A batch whose ticks are "2..4 full-frame videos of one geometry, then something else" (a rotated logo, overlays, a fifth layer): how many
-// leading layers of EVERY tick the streaming kernel takes as a launch of its own (cleared), the rest following in a second launch that continues
-// on the canvas — the layer-by-layer semantics already are that (the canvas is re-quantised between layers either way).  0: no.
-// The point: one layer the strip machinery has to apply per pixel (KINDS bit 3) otherwise puts the WHOLE tick on the strip kernel's most general
-// instantiation (four waves per SIMD): the pipeline tick + a rotated logo 1.268 ms per 128 ticks against 0.62 for its four videos alone.
-int split_stream_prefix(const DTick *ticks, const DLayer *layers, int n_ticks) {
-    if (n_ticks < 1 || !switches().stream.load(std::memory_order_relaxed) || switches().bgra_path.load(std::memory_order_relaxed) != 0) return 0;
-    if (switches().force_general.load(std::memory_order_relaxed)) return 0;
-    int least = 1 << 30;
-    for (int i = 0; i < n_ticks; i++) least = std::min(least, ticks[i].n_layers);
-    std::vector<DTick> head(ticks, ticks + n_ticks);
-    for (int k = std::min(4, least - 1); k >= 2; k--) {            // (every tick keeps at least one layer for the second launch)
-        for (int i = 0; i < n_ticks; i++) head[(size_t)i].n_layers = k;
-        if (bgra_stream_eligible(head.data(), layers, n_ticks)) return k;
-    }
-    return 0;
-}
-int fast_path_stream_bgra() { return FP_STREAM; }
-// the path of a split batch's second launch
-int select_tail_path(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks) {
-    const int p = select_fast_path(target_format, ticks, layers, n_ticks, false);
-    if (p == FP_NONE && target_format == TF_BGRA && !switches().force_general.load(std::memory_order_relaxed) &&
-        wave_layers_eligible(TF_BGRA, ticks, layers, n_ticks, true)) return FP_WAVE_LAYERS;
-    return p;
-}
-
-bool fast_path_is_wave(int path) { return path == FP_WAVE_LAYERS || path == FP_WAVE_NV12 || path == FP_WAVE_Y420P; }
-bool fast_path_by_value(int path) { return path == FP_STREAM || path == FP_STREAM_NV12 || path == FP_STREAM_Y420P || path == FP_NV12_BGRA_TILED || path == FP_Y420P_BGRA_TILED || path == FP_CLEAR_BGRA; }
 
 hipError_t launch_tick_fast(int path, const DTick *ticks_host, const DLayer *layers_host,
                             const DTick *ticks, const DLayer *layers, int n_ticks,

@@ -14,7 +14,7 @@
 // apply_layer_bgra / tick_bgra_wave (the blend result of a layer is rounded to codes exactly as its store would round it), so the
 // same bytes.
 //
-// Eligibility is decided on the host (launch_bgra_stream_eligible): cleared BGRA canvas, every tick the same number (<= 4) of NV12
+// Eligibility is decided on the host (tick_route.cpp: bgra_stream_eligible): cleared BGRA canvas, every tick the same number (<= 4) of NV12
 // layers, layers 1.. flagged LF_SAME_GEOM, axis-aligned bounded matrices without flips, no fill paint, opacities in [0, 1],
 // horizontal reduction <= 1.7 (a strip's source bytes fit the ring's 128-byte rows), plane rows a multiple of 16 bytes.
 #include "kernels_stream_body.hip.inc"
@@ -54,59 +54,11 @@ __global__ __launch_bounds__(64 * ST_WAVES, CHV_STREAM_WAVES) void tick_bgra_str
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-static bool stream_plane_ok(const DPlane &p) {
-    return (((uintptr_t)p.ptr) & 15) == 0 && (p.pitch & 15) == 0 && ((p.w * p.comps) & 15) == 0 && p.w * p.comps >= 16 && p.h >= 1;
-}
-
-// every tick: cleared canvas, the same number (1..4) of NV12 -> BGRA layers of one geometry, axis-aligned and bounded, no flips, no fill,
-// opacities in [0, 1], a strip's source columns within one 128-byte ring row
+// (which launches take these kernels — bgra_stream_eligible —: tick_route.cpp)
 #define CHV_STR2(x) #x
 #define CHV_STR(x) CHV_STR2(x)
 // what this translation unit was built with (chv_build_flags; a timing-only CHV_ST_ABL build must never ship)
 const char *bgra_stream_build_flags() { return "tick_bgra_stream:abl=" CHV_STR(CHV_ST_ABL) ",strips_per_block=" CHV_STR(CHV_STREAM_BLOCK) ",rounds=" CHV_STR(CHV_STREAM_ROUNDS); }
-
-bool bgra_stream_eligible(const DTick *ticks, const DLayer *layers, int n_ticks) {
-    if (n_ticks < 1 || !switches().stream.load(std::memory_order_relaxed)) return false;
-    const int nl = ticks[0].n_layers;
-    if (nl < 1 || nl > 4) return false;
-    for (int i = 0; i < n_ticks; i++) {
-        const DTick &T = ticks[i];
-        if (T.n_layers != nl || !T.clear_first) return false;
-        if ((((uintptr_t)T.dst.pl[0].ptr) & 3) != 0 || (T.dst.pl[0].pitch & 3) != 0) return false;
-        for (int l = 0; l < nl; l++) {
-            const DLayer &Y = layers[T.first_layer + l];
-            // (NV12 or planar sources, one class per launch: LF_SAME_GEOM already says so inside a tick)
-            const int kind0 = layers[ticks[0].first_layer].kind;
-            if ((kind0 != LK_BGRA_FROM_NV12 && kind0 != LK_BGRA_FROM_Y420P) || Y.kind != kind0) return false;
-            const bool planar = kind0 == LK_BGRA_FROM_Y420P;
-            const int need = LF_AXIS_ALIGNED | LF_BOUNDED | LF_NO_FILL | (l ? LF_SAME_GEOM : 0);
-            if ((Y.flags & need) != need) return false;
-            const float op = Y.u[U_OPACITY];
-            if (!(op >= 0.f && op <= 1.f)) return false;
-            if (!stream_plane_ok(Y.src.pl[0]) || !stream_plane_ok(Y.src.pl[1])) return false;
-            if (Y.src.pl[0].h > 32767 || Y.src.pl[1].h > 16383) return false;          // (the row table packs tap rows into 16 / 15 signed bits)
-            if (Y.src.pl[1].comps != (planar ? 1 : 2) || Y.src.pl[0].comps != 1) return false;
-            if (planar) {
-                const DPlane &cu = Y.src.pl[1], &cv = Y.src.pl[2];
-                if (!stream_plane_ok(cv) || cv.comps != 1 || cv.w != cu.w || cv.h != cu.h || cv.pitch != cu.pitch) return false;       // one ring geometry for U and V
-            }
-            if (l == 0) {
-                // source texels per canvas pixel: u = (x / W * 2 - 1) * T0 * X0 + ...  =>  du/dx * w = 2 T0 X0 w / W
-                const double kx = 2.0 * (double)Y.u[U_TRANSFORM + 0] * (double)Y.u[U_TEXTURE + 0], ky = 2.0 * (double)Y.u[U_TRANSFORM + 5] * (double)Y.u[U_TEXTURE + 5];
-                if (!(kx > 0.0) || !(ky > 0.0)) return false;                                   // flips: the rings assume rising positions
-                const double sx = kx * Y.src.pl[0].w / (double)T.W;
-                if (!(63.0 * sx + 2.0 + 15.0 + 1.0 <= 128.0)) return false;                     // luma bytes of a strip (NV12 chroma: the same count)
-                if (planar && !(63.0 * (kx * Y.src.pl[1].w / (double)T.W) + 2.0 + 15.0 + 1.0 <= (double)ST_CPP)) return false;     // a plane's chroma bytes of a strip
-                // source rows per canvas row: the rings are advanced batch by batch (four luma rows per load), so the work per canvas row grows
-                // with the vertical reduction — a picture squeezed into a few canvas rows (a zoom animation's first frames) would issue
-                // hundreds of loads of rows nobody taps per canvas row, and tick_bgra_wave culls by bounding box instead
-                const double sy = ky * Y.src.pl[0].h / (double)T.H;
-                if (!std::isfinite(sy) || sy > 4.0) return false;
-            }
-        }
-    }
-    return true;
-}
 
 // ticks == nullptr: one tick, launched with its descriptors (ticks_host[0], layers_host) as kernel arguments
 hipError_t launch_bgra_stream(const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers, int n_ticks, int maxW, int maxH, hipStream_t stream) {

@@ -63,7 +63,7 @@ constexpr int ST_YL = 4 * ST_PITCH, ST_CL = 2 * ST_PITCH;       // bytes of one 
 // Planar sources (y420p: what FFmpeg's software decoders emit, dec.video.ffmpeg.swift:187-221): the chroma region holds U rows and, behind
 // them, V rows — each [2 batch slots][NL layers][2 rows][96] (a strip's chroma texels at up to 1.7 : 1 fit six vectors) — filled by one load
 // instruction per plane kind (NL x 2 rows x 6 vectors = 48 lanes at four layers).
-constexpr int ST_CPP = 96, ST_CLP = 2 * ST_CPP;                 // planar chroma: bytes per ring row, bytes of one layer inside a batch slot
+constexpr int ST_CLP = 2 * ST_CPP;                              // planar chroma: ST_CPP (tick_route.h) bytes per ring row; bytes of one layer inside a batch slot
 template <int NL, bool PL> constexpr int st_layer_bytes() { return ST_PITCH * ST_YROWS + (PL ? 2 * 2 * ST_CLP : ST_PITCH * ST_CROWS); }       // per layer: 1536 / 1792
 constexpr int ST_TAB = 32;                    // row entries computed at a time (lane = row)
 #ifndef CHV_STREAM_BLOCK

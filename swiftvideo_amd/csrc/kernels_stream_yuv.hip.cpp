@@ -30,7 +30,7 @@
 // kind), so the bytes are those of oracle/ref_kernels.c::px_yuv_to_yuv / px_rgb_to_yuv / px_rgb_to_yuv_int, layer by layer.  Every row
 // loop of this file takes it from yuv_rows.hip.h; here are the places of the taps and the forms only this kernel has (fast_rgb_trip, ys_put_raw_k).
 //
-// Eligibility (yuv_stream_eligible): cleared canvas with W % 8 == 0 and H % 4 == 0, 1..4 layers, every layer axis-aligned, bounded,
+// Eligibility (tick_route.cpp: yuv_stream_eligible): cleared canvas with W % 8 == 0 and H % 4 == 0, 1..4 layers, every layer axis-aligned, bounded,
 // without fill paint and without flips, horizontal reduction <= 1.7 (YUV) / 1.17 (RGB), vertical <= 2.1 (a step of 8 rows must span at most 15 source rows: yuv_stream_eligible), source rows a multiple of
 // 16 bytes, at most 16 KB of rings per wave.  Everything else keeps tick_yuv_wave.
 #include "wave_common.hip.h"
@@ -89,11 +89,9 @@ constexpr int YS_WAVES = CHV_YS_BLOCK;
 constexpr int YS_TAB = 32;                       // row entries per table fill (lane = row)
 // per layer: packed (row positions + flags), luma / RGB row weight, chroma row weight — 16 dwords each — and two dwords per 8-row step
 constexpr int YS_TAB_DW = 3 * YS_TAB + 2 * (YS_TAB / 8);
-constexpr int YS_TAB_BYTES = YS_TAB_DW * 4;
-constexpr int YS_MAXL = 4;
-
-// kinds a launch contains (template parameter KINDS; the instantiation holds no code for the others)
-enum { YK_NV12 = 1, YK_PLANAR = 2, YK_RGB = 4, YK_RGBINT = 8 };
+static_assert(YS_TAB_DW * 4 == YS_TAB_BYTES, "tick_route.h: ys_wave_bytes counts a layer's row tables");
+// (YS_MAXL, the layers per tick, and YK_*, the kinds a launch contains — template parameter KINDS; the instantiation holds no code for the
+// others —: tick_route.h)
 
 // ---- ring classes: rows of PV vectors, filled B rows at a time (one load instruction), NB batches; SPLIT > 0: vectors [0, SPLIT) of a row come
 //      from plane a, the rest from plane b (planar chroma: a U row and a V row side by side).  Rows lie linearly: position p at p x PITCH. ----
@@ -107,16 +105,13 @@ struct RingClass {
 using RingY = RingClass<8, 8, 3, 0>;             // luma: 24 rows x 128 B, eight rows per load
 using RingC2 = RingClass<8, 4, 3, 0>;            // NV12 chroma: 12 rows of (u, v) pairs
 using RingCP = RingClass<12, 4, 3, 6>;           // planar chroma: 12 rows of U (96 B) | V (96 B)
-// RGB texels, rows of 320 B: four batches of three rows in RGB-only launches (the encoder side), of two rows where video layers share the LDS
-// (a mixer's overlays: the ring follows every row, and with two batches of three a row's request was two rows ahead of its taps — 600 ns of
-// waiting per overlay row)
+// RGB texels, rows of 320 B, four batches of ys_rgb_b(KINDS) rows (tick_route.h)
 template <int B> using RingRGB = RingClass<20, B, 4, 0>;
-constexpr int ys_rgb_b(int kinds) { return (kinds & (YK_NV12 | YK_PLANAR)) ? 2 : 3; }
+// (ys_layer_bytes_c, a layer's ring bytes: tick_route.h, from these)
+static_assert(RingY::BYTES == YS_RING_Y_BYTES && RingC2::BYTES == YS_RING_C2_BYTES && RingCP::BYTES == YS_RING_CP_BYTES && RingRGB<2>::PITCH == YS_RING_RGB_PITCH &&
+              RingRGB<2>::BYTES == ys_layer_bytes_c(true, false, 2) && RingRGB<3>::BYTES == ys_layer_bytes_c(true, false, 3), "tick_route.h: the rings' byte counts");
 
 CHV_DEV bool ys_is_rgb(int kind) { return kind == LK_YUV_FROM_RGB || kind == LK_YUV_FROM_RGB_INT; }
-constexpr int ys_layer_bytes_c(bool rgb, bool planar, int rgb_b) {
-    return rgb ? rgb_b * 4 * 320 : RingY::BYTES + (planar ? RingCP::BYTES : RingC2::BYTES);
-}
 
 struct RingState {
     int a0;          // first virtual source row of the window (rows -1 .. h: CLAMP_TO_EDGE through the row of the address); far below 0: not started
@@ -1004,118 +999,7 @@ void tick_yuv_stream_one(const YsOne<NL> a, int strips_x, int chunks_y, int rows
 #define CHV_STR(x) CHV_STR2(x)
 const char *yuv_stream_build_flags() { return "tick_yuv_stream:abl=" CHV_STR(CHV_YS_ABL) ",strips_per_block=" CHV_STR(CHV_YS_BLOCK) ",rounds=" CHV_STR(CHV_YS_ROUNDS) ",carry=" CHV_STR(CHV_YS_CARRY); }
 
-static bool ys_plane_ok(const DPlane &p) {
-    return p.ptr && (((uintptr_t)p.ptr) & 15) == 0 && (p.pitch & 15) == 0 && ((p.w * p.comps) & 15) == 0 && p.w * p.comps >= 16 && p.h >= 1 && p.h <= 8190 &&
-           (long)p.pitch * p.h < (1L << 31);
-}
-static bool ys_kind_rgb(int k) { return k == LK_YUV_FROM_RGB || k == LK_YUV_FROM_RGB_INT; }
-
-// source classes of a launch (template parameter KINDS) and the LDS a wave needs for its widest tick
-struct YsPlan { int kinds, nl, wave_bytes; };
-static YsPlan ys_plan(const DTick *ticks, const DLayer *layers, int n_ticks) {
-    YsPlan p{ 0, 1, 0 };
-    for (int i = 0; i < n_ticks; i++) {
-        p.nl = std::max(p.nl, ticks[i].n_layers);
-        for (int l = 0; l < ticks[i].n_layers; l++) {
-            const int k = layers[ticks[i].first_layer + l].kind;
-            p.kinds |= k == LK_YUV_FROM_NV12 ? YK_NV12 : k == LK_YUV_FROM_Y420P ? YK_PLANAR : k == LK_YUV_FROM_RGB ? YK_RGB : YK_RGBINT;
-        }
-    }
-    return p;
-}
-// the instantiation a launch runs: (kinds, layers) rounded up to what is compiled
-static void ys_round(int tf, YsPlan &p) {
-    const int own = tf == TF_NV12 ? YK_NV12 : YK_PLANAR;
-    if (p.kinds == own) p.nl = p.nl <= 1 ? 1 : p.nl <= 2 ? 2 : 4;
-    else if (p.kinds == YK_RGBINT && p.nl == 1) { }
-    else if ((p.kinds & ~(own | YK_RGB)) == 0) { p.kinds = own | YK_RGB; p.nl = p.nl <= 3 ? 3 : 4; }
-    else { p.kinds = YK_NV12 | YK_PLANAR | YK_RGB | YK_RGBINT; p.nl = 4; }
-    if (p.kinds == own && p.nl == 4) { p.kinds = own | YK_RGB; }
-}
-static int ys_wave_bytes(const YsPlan &p, const DTick *ticks, const DLayer *layers, int n_ticks) {
-    const int nb = ys_rgb_b(p.kinds);
-    int rings = 0;
-    for (int i = 0; i < n_ticks; i++) {
-        int r = 0;
-        for (int l = 0; l < ticks[i].n_layers; l++) {
-            const int k = layers[ticks[i].first_layer + l].kind;
-            // (the kernel's own rule: a launch without RGB kinds / without YUV kinds never asks the layer)
-            const bool rgb = (p.kinds & (YK_RGB | YK_RGBINT)) && (!(p.kinds & (YK_NV12 | YK_PLANAR)) || ys_kind_rgb(k));
-            const bool planar = !rgb && (p.kinds & YK_PLANAR) && (!(p.kinds & YK_NV12) || k == LK_YUV_FROM_Y420P);
-            r += ys_layer_bytes_c(rgb, planar, nb);
-        }
-        rings = std::max(rings, r);
-    }
-    return rings + p.nl * YS_TAB_BYTES;
-}
-
-// transient: one tick, launched once (chv_composite / chv_run_kernel)
-bool yuv_stream_eligible(int tf, const DTick *ticks, const DLayer *layers, int n_ticks, bool transient) {
-    const int mode = switches().yuv_stream.load(std::memory_order_relaxed);
-    if (n_ticks < 1 || !mode) return false;
-    if (tf != TF_NV12 && tf != TF_Y420P) return false;
-    if (mode == 1) {
-        // Where the streaming kernel is the faster one today (profiles/r04_notes.md; same-call A/Bs against tick_yuv_wave):
-        //   * launches whose layers are all integer-matrix RGB pictures — the encoder side's full-frame conversion: 0.567 against 0.640 ms per
-        //     128 frames of 1080p BGRA -> NV12, a lone frame 13.3 against 16.7 us;
-        //   * lone ticks of video layers only (descriptors as kernel arguments, 4- to 16-row chunks): 13.9 against 15.4 us for a 1080p tick.
-        // Batches of video layers are level (0.378 against 0.354 ms per 128 ticks) and stay with the strip kernel; ticks with float RGB
-        // overlays are slower through the rings (a 1080p mixer tick: 31.8 against 21.4 us; 1.08 against 0.65 ms per 128) and stay there too.
-        bool all_int = true, any_rgb = false;
-        for (int i = 0; i < n_ticks; i++)
-            for (int l = 0; l < ticks[i].n_layers; l++) {
-                const int k = layers[ticks[i].first_layer + l].kind;
-                all_int = all_int && k == LK_YUV_FROM_RGB_INT;
-                any_rgb = any_rgb || k == LK_YUV_FROM_RGB || k == LK_YUV_FROM_RGB_INT;
-            }
-        if (!(all_int || (transient && n_ticks == 1 && !any_rgb))) return false;
-    }
-    for (int i = 0; i < n_ticks; i++) {
-        const DTick &T = ticks[i];
-        if (!T.clear_first || T.n_layers < 1 || T.n_layers > YS_MAXL) return false;
-        if ((T.W & 7) || (T.H & 3) || T.W < 8 || T.H < 4 || T.dst.pl[0].w != T.W || T.dst.pl[0].h != T.H) return false;
-        const int np = tf == TF_NV12 ? 2 : 3;
-        for (int p = 0; p < np; p++) {
-            const DPlane &P = T.dst.pl[p];
-            if (!P.ptr || (((uintptr_t)P.ptr) & 3) || (P.pitch & 3)) return false;
-            if (p > 0 && (P.w != T.W / 2 || P.h != T.H / 2)) return false;
-        }
-        for (int l = 0; l < T.n_layers; l++) {
-            const DLayer &Y = layers[T.first_layer + l];
-            const bool rgb = ys_kind_rgb(Y.kind), nv12 = Y.kind == LK_YUV_FROM_NV12, planar = Y.kind == LK_YUV_FROM_Y420P;
-            if (!(rgb || nv12 || planar)) return false;
-            if (nv12 && tf != TF_NV12) return false;
-            const int need = LF_AXIS_ALIGNED | LF_BOUNDED | LF_NO_FILL;
-            if ((Y.flags & need) != need) return false;
-            if (!(Y.u[U_OPACITY] - Y.u[U_OPACITY] == 0.f)) return false;
-            const int npl = rgb ? 1 : nv12 ? 2 : 3;
-            for (int p = 0; p < npl; p++) if (!ys_plane_ok(Y.src.pl[p])) return false;
-            if (rgb && Y.src.pl[0].comps != 4) return false;
-            if (!rgb && (Y.src.pl[0].comps != 1 || Y.src.pl[1].comps != (nv12 ? 2 : 1))) return false;
-            if (planar && (Y.src.pl[2].w != Y.src.pl[1].w || Y.src.pl[2].h != Y.src.pl[1].h || Y.src.pl[2].pitch != Y.src.pl[1].pitch || Y.src.pl[2].comps != 1)) return false;
-            // source texels per canvas pixel: u = (x / W * 2 - 1) * T0 * X0 + ...  =>  du/dx * w = 2 T0 X0 w / W
-            const double kx = 2.0 * (double)Y.u[U_TRANSFORM + 0] * (double)Y.u[U_TEXTURE + 0], ky = 2.0 * (double)Y.u[U_TRANSFORM + 5] * (double)Y.u[U_TEXTURE + 5];
-            if (!(kx > 0.0) || !(ky > 0.0)) return false;                                   // flips: the rings assume rising positions
-            const double sxr = kx * Y.src.pl[0].w / (double)T.W, syr = ky * Y.src.pl[0].h / (double)T.H;
-            // An 8-row step asks the 24-row luma ring for the rows ry(row 0) .. ry(row 7) + 1, and ring_ensure holds hi - lo <= ROWS - B = 16:
-            // ry(7) - ry(0) <= ceil(7 * syr) must stay <= 15, i.e. syr < 15 / 7 = 2.143 (at 2.2 a step could span 17 rows and row 7 would tap a
-            // slot already holding the row 24 below: stale luma).  2.1 is the bound the fixed cases and the fuzzers exercise.
-            if (!std::isfinite(sxr) || !std::isfinite(syr) || syr > 2.1) return false;
-            // bytes of a ring row a strip's taps span: 63 steps + tap 1 + rounding slack, the start's alignment
-            if (rgb) { if (!((63.0 * sxr + 3.0) * 4.0 + 12.0 <= 320.0)) return false; }
-            else {
-                if (!(63.0 * sxr + 3.0 + 15.0 <= 128.0)) return false;                      // luma; NV12 chroma: half the texels, two bytes each
-                const double sxc = kx * Y.src.pl[1].w / (double)T.W;
-                if (nv12 && !((63.0 * sxc + 3.0) * 2.0 + 14.0 <= 128.0)) return false;
-                if (planar && !(63.0 * sxc + 3.0 + 15.0 <= 96.0)) return false;
-            }
-        }
-    }
-    YsPlan p = ys_plan(ticks, layers, n_ticks);
-    ys_round(tf, p);
-    // (a wave's rings and tables: beyond 16 KB the LDS holds fewer than ten waves per CU, and the strip kernel is the better choice)
-    return ys_wave_bytes(p, ticks, layers, n_ticks) <= 16 * 1024;
-}
+// (which launches take these kernels — yuv_stream_eligible — and ys_plan / ys_round / ys_wave_bytes, the instantiation and the LDS of one: tick_route.cpp)
 
 template <int TF, int NL, int KINDS>
 static void ys_launch(dim3 grid, size_t lds, hipStream_t stream, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers,

@@ -526,86 +526,8 @@ extern template hipError_t launch_yuv_wave_t<true>(CHV_YUV_WAVE_ARGS);          
 
 
 // ---------------------------------------------------------------------------
-// host side: eligibility and launch of both wave kernels
+// host side: launch of both wave kernels (eligibility and the launch plan — wave_layers_eligible, plan_wave_layers —: tick_route.cpp)
 // ---------------------------------------------------------------------------
-static bool finite16w(const float *m) {
-    for (int i = 0; i < 16; i++) if (!(m[i] - m[i] == 0.f)) return false;
-    return true;
-}
-// (pitch < 2^24: the staging address arithmetic uses 24-bit multiplies)
-static bool aligned16w(const DPlane &p) { return (((uintptr_t)p.ptr) & 15) == 0 && (p.pitch & 15) == 0 && p.w * p.comps >= 16 && p.pitch < (1 << 24) && p.h < (1 << 24); }
-static bool host_src_rgb(int kind) { return kind == LK_BGRA_FROM_RGB || kind == LK_YUV_FROM_RGB || kind == LK_YUV_FROM_RGB_INT; }
-static bool host_src_planar(int kind) { return kind == LK_BGRA_FROM_Y420P || kind == LK_YUV_FROM_Y420P; }
-static bool host_src_nv12(int kind) { return kind == LK_BGRA_FROM_NV12 || kind == LK_YUV_FROM_NV12; }
-
-struct WaveDims { int p0pitch, p0rows, p1pitch, p1rows; };
-static int strip_rows(int) { return 8; }      // (the height every eligible tick must fit; launches may pick 16, see launch_wave_layers)
-
-// LDS rectangles one strip of this layer can touch, from the layer's scale factors
-// rows of slack in a staged rectangle beyond ceil(strip rows x vertical ratio): tap row 1, and the ratio's rounding on both sides
-#ifndef CHV_P0ROWS_SLACK
-#define CHV_P0ROWS_SLACK 3
-#endif
-static WaveDims wave_dims(const DTick &T, const DLayer &L, int WTH) {
-    const float *U = L.u;
-    double sxr = std::fabs((double)U[U_TEXTURE + 0] * (double)U[U_TRANSFORM + 0] * 2.0 / (double)T.W);
-    double syr = std::fabs((double)U[U_TEXTURE + 5] * (double)U[U_TRANSFORM + 5] * 2.0 / (double)T.H);
-    WaveDims d{ 0, 0, 0, 0 };
-    const bool rgb = host_src_rgb(L.kind), planar = host_src_planar(L.kind);
-    const int bpt0 = rgb ? 4 : 1;
-    int span0 = (int)std::ceil(WTW * sxr * L.src.pl[0].w) + 4;           // texels incl. tap 1 and rounding slack
-    d.p0pitch = ((span0 * bpt0 + 15) / 16 + 3) * 16;                      // vectors + alignment + 2 pad vectors
-    // (rectangles taller than two rows per strip row are staged as the rows' own tap-row pairs: WGeom::pair, wave_common.hip.h)
-    d.p0rows = std::min((int)std::ceil(WTH * syr * L.src.pl[0].h) + CHV_P0ROWS_SLACK, (CHV_WAVE_PAIR && WTH == 8) ? 2 * WTH : (1 << 30));
-    if (!rgb) {
-        const int bpt1 = planar ? 1 : 2;
-        int span1 = (int)std::ceil(WTW * sxr * L.src.pl[1].w) + 4;
-        d.p1pitch = ((span1 * bpt1 + 15) / 16 + 3) * 16;
-        d.p1rows = std::min((int)std::ceil(WTH * syr * L.src.pl[1].h) + 3, (CHV_WAVE_PAIR && WTH == 8) ? 2 * WTH : (1 << 30));
-    }
-    return d;
-}
-static size_t wave_lds(const WaveDims &d, bool planar, int target_format, int rows) {
-    return            (size_t)WAVES * ((size_t)rows * 48 + (size_t)d.p0pitch * d.p0rows + (size_t)d.p1pitch * d.p1rows * (planar ? 2 : 1));
-}
-
-// tail: the launch continues on canvases another launch has composed (the second part of a split batch): strips no layer touches leave at once,
-// so the strip kernel is the better choice also where every layer needs the per-pixel path
-bool wave_layers_eligible(int target_format, const DTick *ticks, const DLayer *layers, int n_ticks, bool tail) {
-    bool any_general = false, any_staged = false;
-    for (int i = 0; i < n_ticks; i++) {
-        const DTick &T = ticks[i];
-        if (T.n_layers < 1 || T.clear_first != ticks[0].clear_first) return false;
-        if (target_format == TF_BGRA) {
-            if (!aligned16w(T.dst.pl[0])) return false;
-        } else {
-            // 4:2:0: even canvas, chroma planes exactly half size (odd sizes, where gid/2 leaves the chroma plane, stay on the general kernel)
-            const int np = target_format == TF_NV12 ? 2 : 3;
-            if ((T.W & 1) || (T.H & 1) || T.dst.pl[0].w != T.W || T.dst.pl[0].h != T.H) return false;
-            for (int p = 1; p < np; p++) if (T.dst.pl[p].w != T.W / 2 || T.dst.pl[p].h != T.H / 2) return false;
-        }
-        for (int l = 0; l < T.n_layers; l++) {
-            const DLayer &L = layers[T.first_layer + l];
-            const bool rgb = host_src_rgb(L.kind), nv12 = host_src_nv12(L.kind), planar = host_src_planar(L.kind);
-            // img_bgra_bgra (kernels.metal:52-62 — what an unchanged VideoMixer.findKernel resolves a BGRA layer on a BGRA canvas to):
-            // nearest sampling, nothing to stage; applied per pixel inside the wave kernel like a rotated layer, so that a
-            // reference-default tick of video layers + a BGRA overlay keeps the strip path for its video layers
-            if (L.kind == LK_BGRA_METAL && target_format == TF_BGRA) { any_general = true; continue; }
-            if (!(rgb || nv12 || planar)) return false;
-            // layers that cannot be staged (rotation, shear, unbounded matrices) are applied per pixel inside the kernel: nothing to check
-            if ((L.flags & (LF_AXIS_ALIGNED | LF_BOUNDED)) != (LF_AXIS_ALIGNED | LF_BOUNDED)) { any_general = true; continue; }
-            any_staged = true;
-            if (!finite16w(L.u + U_TRANSFORM) || !finite16w(L.u + U_TEXTURE) || !finite16w(L.u + U_BORDER)) return false;
-            const int np = rgb ? 1 : nv12 ? 2 : 3;
-            for (int p = 0; p < np; p++) if (!aligned16w(L.src.pl[p])) return false;
-            if (planar && (L.src.pl[2].w != L.src.pl[1].w || L.src.pl[2].h != L.src.pl[1].h)) return false;   // one staging geometry for U and V
-            if (wave_lds(wave_dims(T, L, strip_rows(target_format)), planar, target_format, strip_rows(target_format)) > (size_t)LDS_BUDGET) return false;
-        }
-    }
-    // (a launch whose layers ALL need the per-pixel path gains nothing here: the general kernel it is)
-    return any_staged || !any_general || tail;
-}
-
 #define CHV_STR2(x) #x
 #define CHV_STR(x) CHV_STR2(x)
 const char *yuv_wave_build_flags() { return "tick_yuv_wave:abl=" CHV_STR(CHV_ABL) ",strip_rows=8|16"; }
@@ -650,115 +572,6 @@ hipError_t launch_geom_precompute(const GeomConfig &cfg, const GeomJob *jobs, in
     else hipLaunchKernelGGL(geom_precompute<8>, dim3((unsigned)blocks), dim3(64), rowtab_lds, stream, jobs, n_jobs,
                             cfg.p0pitch, cfg.p0rows, cfg.p1pitch, cfg.p1rows, cfg.planar_any);
     return hipGetLastError();
-}
-
-// What a launch of the strip kernels is shaped like — strip height, LDS layout, source classes — from its descriptors alone (launch_wave_layers
-// launches with it; the store asks for it through wave_geom_config before the descriptors go to the device: the tables it looks up were built
-// for one shape).
-struct WavePlan { int WTH; WaveDims m; bool planar; int kinds, side; size_t lds; };
-static WavePlan plan_wave_layers(int target_format, const DTick *ticks_host, const DLayer *layers_host, int n_ticks, int maxW, int maxH) {
-    // Strip height.  16 rows when the launch has enough strips to fill the chip's wave slots with them and the taller
-    // rectangles leave room for two strips per 64 KB of LDS; on BGRA canvases (whose 16-row instantiation has no masked rows:
-    // registers) only when every layer covers (almost) the whole canvas, so that hardly any strip is crossed by a layer's
-    // edge.  8 rows otherwise.  CHV_WAVE_ROWS=8|16 is the A/B and test switch.
-    int WTH = strip_rows(target_format);
-    {
-        const int forced = switches().wave_rows.load(std::memory_order_relaxed);
-        bool tall = (long)n_ticks * ((maxW + WTW - 1) / WTW) * ((maxH + 15) / 16) >= 8192;
-        if (target_format == TF_BGRA) {
-            for (int i = 0; i < n_ticks && tall; i++) {
-                const DTick &T = ticks_host[i];
-                for (int l = 0; l < T.n_layers && tall; l++) {
-                    const int32_t *bb = layers_host[T.first_layer + l].bbox;
-                    tall = (double)(bb[2] - bb[0]) * (double)(bb[3] - bb[1]) >= 0.9 * (double)T.W * (double)T.H;
-                }
-            }
-        }
-        if (forced == 8 || forced == 16) tall = forced == 16;
-        if (tall) WTH = 16;
-    }
-    WaveDims m{ 0, 0, 0, 0 };
-    bool planar = false;
-    int kinds = 0;               // source classes in the launch: bit 0 NV12, bit 1 y420p, bit 2 RGB
-    auto measure = [&](int rows) {
-        m = WaveDims{ 0, 0, 0, 0 };
-        planar = false;
-        for (int i = 0; i < n_ticks; i++) {
-            for (int l = 0; l < ticks_host[i].n_layers; l++) {
-                const DLayer &L = layers_host[ticks_host[i].first_layer + l];
-                if (L.kind == LK_BGRA_METAL || (L.flags & (LF_AXIS_ALIGNED | LF_BOUNDED)) != (LF_AXIS_ALIGNED | LF_BOUNDED)) { kinds |= 8; continue; }     // not staged
-                WaveDims d = wave_dims(ticks_host[i], L, rows);
-                m.p0pitch = std::max(m.p0pitch, d.p0pitch); m.p0rows = std::max(m.p0rows, d.p0rows);
-                m.p1pitch = std::max(m.p1pitch, d.p1pitch); m.p1rows = std::max(m.p1rows, d.p1rows);
-                planar = planar || host_src_planar(L.kind);
-                kinds |= host_src_rgb(L.kind) ? 4 : host_src_planar(L.kind) ? 2 : 1;
-            }
-        }
-        return wave_lds(m, planar, target_format, rows);
-    };
-    size_t lds = measure(WTH);
-    if (WTH == 16 && lds > (size_t)LDS_BUDGET / 2) { WTH = 8; lds = measure(WTH); }      // (keep at least two tall strips' worth per 64 KB)
-    // Side-by-side layout: a YUV layer's luma, chroma / U and V rectangles next to each other in the rows of ONE region whose rows are as wide as the
-    // widest need of the launch — an RGB rectangle (the mixer canvas: a video layer's 128 + 96 + 96 bytes in an overlay's 320) or luma + chroma of
-    // the widest video layer — instead of a plane-0 region followed by chroma regions.  The region is then max(rows) x pitch instead of the sum of
-    // the regions; taken where that is smaller (18 -> 23 waves' worth of LDS per CU on the mixer canvas, 20 -> 26 for video + overlays on BGRA).
-    int side = 0;
-    if ((kinds & 3) && lds <= (size_t)LDS_BUDGET) {
-        int yneed = 0, c_nv12 = 0, c_planar = 0;
-        for (int i = 0; i < n_ticks; i++)
-            for (int l = 0; l < ticks_host[i].n_layers; l++) {
-                const DLayer &L = layers_host[ticks_host[i].first_layer + l];
-                if (L.kind == LK_BGRA_METAL || (L.flags & (LF_AXIS_ALIGNED | LF_BOUNDED)) != (LF_AXIS_ALIGNED | LF_BOUNDED) || host_src_rgb(L.kind)) continue;
-                const WaveDims d = wave_dims(ticks_host[i], L, WTH);
-                yneed = std::max(yneed, d.p0pitch);
-                if (host_src_planar(L.kind)) c_planar = std::max(c_planar, d.p1pitch); else c_nv12 = std::max(c_nv12, d.p1pitch);
-            }
-        const int planes = planar ? 2 : 1;
-        const int pitch = std::max(m.p0pitch, yneed + std::max(c_nv12, 2 * c_planar));
-        const size_t separate = (size_t)m.p0pitch * m.p0rows + (size_t)m.p1pitch * m.p1rows * planes;
-        const size_t beside = (size_t)pitch * std::max(m.p0rows, m.p1rows);
-        if (yneed > 0 && beside < separate && (yneed >> 4) < 4096 && (c_planar >> 4) < 4096) {
-            // bits 8-19: luma columns / 16; bits 20-31: columns of ONE planar chroma plane / 16 (0: no planar picture in the launch)
-            side = ((yneed >> 4) << 8) | ((c_planar >> 4) << 20) | (1 << 7);
-            m.p0pitch = pitch;
-            lds = lds - (size_t)WAVES * separate + (size_t)WAVES * beside;
-        }
-    }
-    if (lds > (size_t)LDS_BUDGET) {
-        // per-layer maxima combined exceed the budget: shrink the row counts; rectangles that do not fit fall back to
-        // unstaged taps inside the kernel
-        const size_t fixed = (size_t)WAVES * WTH * 48;     // (row table: WaveCfg::ROWTAB_BYTES)
-        const size_t per_row = (size_t)WAVES * ((size_t)m.p0pitch + (size_t)m.p1pitch * (planar ? 2 : 1));
-        int rows = std::max(1, (int)((LDS_BUDGET - fixed) / per_row));
-        m.p0rows = std::min(m.p0rows, rows); m.p1rows = std::min(m.p1rows, rows);
-        lds = wave_lds(m, planar, target_format, WTH);
-    }
-#ifdef CHV_EXP_LDS_PAD
-    // measurement-only variant (tools/build_variant.sh … -DCHV_EXP_LDS_PAD): extra LDS per block caps the waves per SIMD — how much
-    // occupancy the strip kernels need (profiles/r03_notes.md section 7)
-    if (const char *pad = getenv("CHV_LDS_PAD")) { fprintf(stderr, "[chv] lds %zu + pad %d, rows %d\n", lds, atoi(pad), WTH); lds += (size_t)atoi(pad); }
-#endif
-    m.p0rows = std::min(m.p0rows, 0xFFFF); m.p1rows = std::min(m.p1rows, 0xFFFF);      // (far beyond what LDS holds: such rectangles are not staged anyway)
-    return WavePlan{ WTH, m, planar, kinds, side, lds };
-}
-static GeomConfig plan_config(const WavePlan &P, int target_format, int maxW, int maxH, int n_layers_total) {
-    return GeomConfig{ target_format, P.WTH, P.m.p0pitch, P.m.p0rows, P.m.p1pitch, P.m.p1rows, (P.planar ? 1 : 0) | P.side, (maxW + WTW - 1) / WTW, (maxH + P.WTH - 1) / P.WTH, n_layers_total };
-}
-bool wave_geom_config(int target_format, const DTick *ticks_host, const DLayer *layers_host, int n_ticks, int maxW, int maxH, int n_layers_total,
-                      GeomConfig *cfg) {
-    const WavePlan P = plan_wave_layers(target_format, ticks_host, layers_host, n_ticks, maxW, maxH);
-    *cfg = plan_config(P, target_format, maxW, maxH, n_layers_total);
-    return P.kinds != 4 && (P.kinds & 7) != 0;
-}
-
-// May this lone tick travel as a kernel argument (launch_transient: no descriptor slot, no copy)?  4:2:0 canvases: every instantiation of
-// tick_yuv_wave takes one; BGRA canvases: tick_bgra_wave_one exists for cleared canvases, 8-row strips and launches without per-pixel layers.
-bool wave_layers_by_value(int target_format, const DTick *tick_host, const DLayer *layers_host) {
-    if (tick_host->n_layers < 1 || tick_host->n_layers > WAVE_ONE_LAYERS) return false;
-    if (target_format != TF_BGRA) return true;
-    if (!tick_host->clear_first) return false;
-    const WavePlan P = plan_wave_layers(target_format, tick_host, layers_host, 1, tick_host->W, tick_host->H);
-    return P.WTH == 8 && !(P.kinds & 8) && P.kinds != 4;
 }
 
 hipError_t launch_wave_layers(int target_format, const DTick *ticks_host, const DLayer *layers_host, const DTick *ticks, const DLayer *layers,

@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "device_types.h"
+#include "tick_route.h"
 
 #pragma clang fp contract(off)
 
@@ -455,7 +456,7 @@ __device__ __constant__ const CscAbsorbed kCscAbsorbed[4] = {
     { 0, 0, 0, 0, 0, 0, 0.f, 0.f, 0.f },                                                              // BT.601 full: no such biases
     { 65536, -103206, 12276, 30679, -121609, -223690752, 8400986.0f, -15564928.0f, -9977984.0f },     // BT.709 full: biases 12378, -7176320, -1589376
 };
-constexpr bool csc_absorbable(int csc) { return (csc & 3) != 2; }
+// (csc_absorbable — every matrix but BT.601 full range —: tick_route.h, the host asks it too)
 CHV_DEV CscAbsorbed csc_fold_absorbed(int csc) { return kCscAbsorbed[csc & 3]; }
 // The channels as 16.16 sums clamped to [0, 2^24): the code is byte 2 — as a binary16 read from the register's HIGH half, code x 2^-24
 // (code_h below: the denormal trick of tap_h), which is how tick_bgra_stream's blend consumes it: one v_fma_mix_f32 per channel where

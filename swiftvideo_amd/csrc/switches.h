@@ -19,7 +19,7 @@ struct Switches {
                                          // copy; 1 (host) read from the pinned host ring; 2 (device) the device copy always (A/Bs)
     std::atomic<int> stream{1};          // 0: never tick_bgra_stream (A/B; CHV_BGRA_PATH=stream: also for one-layer ticks)
     std::atomic<int> yuv_stream{1};      // CHV_YUV_STREAM: 0 never tick_yuv_stream (4:2:0 canvases keep tick_yuv_wave); 1 (default) where it measured faster
-                                         // (kernels_stream_yuv.hip.cpp::yuv_stream_eligible); force: every eligible launch (A/Bs and tests)
+                                         // (tick_route.cpp::yuv_stream_eligible); force: every eligible launch (A/Bs and tests)
     std::atomic<int> wave_dma{1};        // CHV_WAVE_DMA: 0 the RGB-only strip kernel stages its rectangles through registers like the others (A/B, and the
                                          // fuzzers' way to the non-DMA staging of that instantiation); 1 (default) by LDS-DMA where the shape allows
     std::atomic<int> geom_cache{1};      // CHV_GEOM_CACHE: 0 the strip kernels compute every layer's per-strip geometry in place also in batches (A/B, and the

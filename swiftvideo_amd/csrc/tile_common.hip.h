@@ -8,8 +8,7 @@
 
 namespace chv {
 
-constexpr int NTHREADS = 256;
-constexpr int LDS_BUDGET = 64 * 1024;
+// (NTHREADS, the tiled kernel's block, and LDS_BUDGET: tick_route.h)
 
 enum { AX_BORDER = 1, AX_TX = 2, AX_UV = 4, AX_ALL = 7 };
 

@@ -10,15 +10,7 @@
 
 namespace chv {
 
-// (WTW, the strip width, and CHV_GEOM_CACHE: geom_cache.h)
-
-// Waves per block.  The waves of a block share nothing but the launch (every wave has its own LDS region and there is no block
-// barrier on the data path), so the block size only sets the granularity at which LDS is handed out: one wave per block
-// (1, 2 and 4 measured the same where LDS is not the limit).
-#ifndef CHV_WAVE_WAVES
-#define CHV_WAVE_WAVES 1
-#endif
-constexpr int WAVES = CHV_WAVE_WAVES;
+// (WTW, the strip width, WAVES = CHV_WAVE_WAVES, the waves per block, and CHV_WAVE_PAIR: tick_route.h; CHV_GEOM_CACHE: geom_cache.h)
 constexpr int WAVE_BLOCK = WAVES * 64;
 // Per strip height H (rows per lane; 8 for BGRA canvases, 16 for 4:2:0 canvases whose codes pack four to a register):
 // staging registers (16-byte vectors) per lane, 64 slots each, sized for the rectangles of a 1.5x downscale (YUV) / of a
@@ -90,9 +82,6 @@ struct WGeom : StageGeom {
     int pair;
     int r_hi1;                   // pair form: the last first-tap row the rectangle was validated for (clamp of a row's own tap row)
 };
-#ifndef CHV_WAVE_PAIR
-#define CHV_WAVE_PAIR 1
-#endif
 // source row of LDS row r (before CLAMP_TO_EDGE).  Pair form (PAIR instantiations only: stage_impl<EDGE, true>): `pry` holds, in lane j, strip row
 // j's first tap row; executed by ALL lanes (a lane shuffle).  (Kept out of the other instantiations altogether — and free of pointers: a first
 // version that looked the rows up in the LDS row table through a pointer argument made hipcc fetch every plane descriptor field with vector

@@ -295,9 +295,9 @@ def _vector_planes_ok(pl):
 
 def forbidden_routes(recorder, ticks, split=False):
     """names of the vector routes that these ticks must NOT be launched through, given where their pictures lie: a route is forbidden when a
-    plane its predicate requires at a 16-byte address and pitch is not (kernels_stream.hip.cpp::stream_plane_ok, kernels_stream_yuv.hip.cpp::
-    ys_plane_ok: every source plane; kernels_wave_yuv.hip.cpp::aligned16w: a BGRA canvas and the sources of every layer that is staged, i.e.
-    axis-aligned — a 4:2:0 canvas is not asked; kernels_fast.hip.cpp::aligned16: canvas and every source plane).  One launch takes all its
+    plane its predicate requires at a 16-byte address and pitch is not (all in tick_route.cpp — stream_plane_ok, tick_bgra_stream's, and
+    ys_plane_ok, tick_yuv_stream's: every source plane; aligned16w, the strip kernels': a BGRA canvas and the sources of every layer that is
+    staged, i.e. axis-aligned — a 4:2:0 canvas is not asked; aligned16, the tiled kernel's: canvas and every source plane).  One launch takes all its
     ticks, so one bad tick forbids the route; of a `split` batch (two launches, each taking some of the ticks) only what every tick forbids."""
     per_tick = []
     for target, clear, layers in ticks:

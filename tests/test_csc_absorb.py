@@ -38,9 +38,10 @@ def test_header_table_is_what_the_search_derives():
             assert got == (0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0), name
         else:
             assert got == tuple(want[:9]), name
-    # BT.601 full range is the one without such biases (csc_absorbable in the header says so)
+    # BT.601 full range is the one without such biases (csc_absorbable says so: tick_route.h, its one definition for the kernels and the route rules)
     assert [r is None for _, r in S.folded_rows()] == [False, False, True, False]
-    assert "constexpr bool csc_absorbable(int csc) { return (csc & 3) != 2; }" in (ROOT / "swiftvideo_amd" / "csrc" / "pixel_math.hip.h").read_text()
+    assert "constexpr bool csc_absorbable(int csc) { return (csc & 3) != 2; }" in (ROOT / "swiftvideo_amd" / "csrc" / "tick_route.h").read_text()
+    assert "csc_absorbable(int" not in (ROOT / "swiftvideo_amd" / "csrc" / "pixel_math.hip.h").read_text()
 
 
 @pytest.mark.parametrize("csc", [0, 1, 3])

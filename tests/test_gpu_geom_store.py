@@ -223,7 +223,7 @@ def test_lone_ticks_carry_their_descriptors_as_kernel_arguments(ctx, switch, dst
 @pytest.mark.parametrize("inset", [False, True])
 def test_lone_one_layer_ticks_on_bgra_canvases_by_route(ctx, switch, vf, canvas, inset):
     """a lone tick of ONE video layer on a cleared BGRA canvas: streaming twin below 1.4 Mpixel, strip twin (tick_bgra_wave_one, KINDS 1 / 2) from
-    there up and for insets the streaming kernel cannot take (kernels_fast.hip.cpp::select_fast_path) — and the tiled twin and the descriptor ring
+    there up and for insets the streaming kernel cannot take (tick_route.cpp::select_fast_path) — and the tiled twin and the descriptor ring
     when asked for: the oracle's canvas every way, four ticks each (in place, building, served from the store)"""
     cw, ch = canvas
     sw, sh = 960, 544

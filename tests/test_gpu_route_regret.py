@@ -1,4 +1,4 @@
-"""Is the kernel the library picks the fast one?  `select_fast_path` (kernels_fast.hip.cpp) is a decision tree with thresholds measured on one
+"""Is the kernel the library picks the fast one?  `select_fast_path` (tick_route.cpp) is a decision tree with thresholds measured on one
 box; every route gives the oracle's bytes (tests/test_gpu_fuzz.py forces each), so a regression in one kernel — or a box where the thresholds
 are off — would silently leave ticks on the slower path.  bench.py's route_regret leg times every route that accepts a default workload's batch
 in one process; here the same leg over the workloads whose routes compete, failing beyond 10 % (the leg's own target, reported by the default

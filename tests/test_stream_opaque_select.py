@@ -17,8 +17,8 @@ def test_selection_predicate(tmp_path):
 
 
 def test_only_the_stream_unit_names_the_new_launcher():
-    """chipvideo.cpp and geom_store.cpp must link without the kernel units (tests/stubhip): launch_bgra_stream is the only caller"""
-    for other in ("chipvideo.cpp", "geom_store.cpp", "kernels_fast.hip.cpp"):
+    """chipvideo.cpp, geom_store.cpp and tick_route.cpp must link without the kernel units (tests/stubhip): launch_bgra_stream is the only caller"""
+    for other in ("chipvideo.cpp", "geom_store.cpp", "tick_route.cpp", "kernels_fast.hip.cpp"):
         assert "launch_bgra_stream_opaque" not in (ROOT / "swiftvideo_amd" / "csrc" / other).read_text(), other
 
 
