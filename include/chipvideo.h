@@ -76,7 +76,8 @@ int chv_debug_set_switch(const char *name, const char *value);
  * chv_scale_lanczos_ladder (process-wide), and "lanczos_420_ladder_launches", the same count for the cross-format path (NV12 -> y420p,
  * y420p -> NV12) of chv_scale_lanczos_420 and chv_scale_lanczos_420_ladder (process-wide; same-format pairs through those entries are forwarded
  * and counted by "lanczos_planar_ladder_launches" or not at all, like the calls they forward to), and "lanczos_to_420_launches", the same count for
- * the five formats chv_scale_lanczos_to_420 and chv_scale_lanczos_to_420_ladder do not forward (process-wide), and "lanczos_from_yuv_launches", the device
+ * the five formats chv_scale_lanczos_to_420 and chv_scale_lanczos_to_420_ladder do not forward (process-wide), and "lanczos_hbd_launches", the same
+ * count for chv_scale_lanczos_hbd_to_420 and chv_scale_lanczos_hbd_to_420_ladder (process-wide), and "lanczos_from_yuv_launches", the device
  * launches made by chv_scale_lanczos_from_yuv and chv_scale_lanczos_from_yuv_batch (process-wide: one per call, one per chunk), and
  * "lanczos_from_yuv_ladder_launches", the device launches made by chv_scale_lanczos_from_yuv_ladder (process-wide: one per chunk for a ladder
  * whose rungs all take one route, two for one with rungs on both; that entry does not touch "lanczos_from_yuv_launches"), and
@@ -129,7 +130,11 @@ const char *chv_kernel_name(int kernel);
 typedef enum chv_pixel_format {
     CHV_FMT_NV12 = 0, CHV_FMT_NV21 = 1, CHV_FMT_YUVS = 2, CHV_FMT_ZVUY = 3,
     CHV_FMT_Y420P = 4, CHV_FMT_Y422P = 5, CHV_FMT_Y444P = 6,
-    CHV_FMT_RGBA = 7, CHV_FMT_BGRA = 8, CHV_FMT_INVALID = 11
+    CHV_FMT_RGBA = 7, CHV_FMT_BGRA = 8, CHV_FMT_INVALID = 11,
+    /* 10-bit 4:2:0 (no reference counterpart: sample.pict.swift:19 leaves them open).  Sources of chv_scale_lanczos_hbd_to_420 only; every other
+     * entry treats them as any unknown format.  chv_plane.components is the BYTES of a texel. */
+    CHV_FMT_P010 = 12,      /* 2 planes: Y (components 2), CbCr (components 4); code = little-endian word >> 6 */
+    CHV_FMT_Y420P10 = 13    /* 3 planes of components 2: Y, Cb, Cr (FFmpeg's yuv420p10le); code = word & 1023 */
 } chv_pixel_format;
 
 /* Integer YUV->RGB matrices for CHV_K_IMG_{NV12,Y420P}_BGRA. */
@@ -558,6 +563,37 @@ int chv_scale_lanczos_420_ladder(chv_context *ctx, const chv_image *dsts, int n_
  * CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) pictures with src_planes of 1, 2 or 3.  A longer list is split along the PICTURES. */
 int chv_scale_lanczos_to_420(chv_context *ctx, const chv_image *dst, const chv_image *src);
 int chv_scale_lanczos_to_420_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
+/* Lanczos-3 from the two 10-bit 4:2:0 formats into the two 8-bit 4:2:0 packings ("hbd": high bit depth): `dst` is an
+ * NV12 or y420p picture exactly as chv_scale_lanczos_420 checks it, `src` a picture of one of
+ *   - CHV_FMT_P010:     2 planes.  Plane 0 is w x h texels of components = 2 (one little-endian 16-bit word: Y), plane 1 is
+ *                       max(1, w / 2) x max(1, h / 2) texels of components = 4 (two words: Cb, then Cr).  The code of a sample is word >> 6; the
+ *                       low six bits are ignored whatever they hold;
+ *   - CHV_FMT_Y420P10:  3 planes of components = 2 (FFmpeg's yuv420p10le): Y, Cb, Cr.  Cb and Cr must agree in size.  The code of a sample is
+ *                       word & 1023; the high six bits are ignored.
+ * The start address (buffer + offset) and the pitch of every source plane must be even.  8-bit sources are not forwarded: this entry has only
+ * its own two formats.
+ * Every source has three LOGICAL images Y, Cb and Cr of 10-bit codes 0..1023.  Each is resampled to the size of the same logical image of dst
+ * exactly as chv_scale_lanczos resamples a 1-component plane: its own tables per axis from its own width and height, horizontal then vertical
+ * pass, fmaf per tap from 0 with taps ascending, indices clamped to the image's edge, float intermediate; the code enters the chain as an
+ * exact float.  The value v that leaves the vertical chain is stored as convert_uchar_sat_rte(v * 0.25f): the product is exact, so this rounds
+ * once, ties to even, and saturates at 255.  No dither, no colour arithmetic, no re-siting, no cross-plane term.  At equal picture sizes
+ * therefore every stored byte is min(rint(code / 4), 255) of the sample at its place: codes 1022 and 1023 give 255, codes 2, 6, 10, ... are ties
+ * and go to the even neighbour.
+ * chv_scale_lanczos_hbd_to_420_ladder: dsts[r * n + i] is rung r of source i; the call writes the bytes of n_rungs x n single calls.  All sources
+ * have one size and one format, all targets one format, all targets of a rung one size.  All or nothing; n_rungs == 0 or n == 0 is a no-op.
+ * Errors (nothing launched, nothing written):
+ *   - as chv_scale_lanczos_420 for dst                                                                            -> CHV_ERR_BAD_TARGET;
+ *   - a source that is neither of the two formats with the plane and component counts above, a source plane that fails a plane check, an odd
+ *     start address or pitch, Cb and Cr of different size                                                         -> CHV_ERR_BAD_INPUT;
+ *   - differing formats or sizes within a list, a bad count, a NULL list with non-zero counts, n_rungs > CHV_LADDER_MAX_RUNGS, a rung for which
+ *     the 160 KB rule of chv_scale_lanczos (applied to sizes, unchanged) refuses any logical image                -> CHV_ERR_INVALID_VALUE;
+ *   - a build without the kernel unit, after validation                                                           -> CHV_ERR_NOT_IMPLEMENTED.
+ * Stream order, upload dependencies, a pass's held work and table lifetime as chv_scale_lanczos_batch.  The entries read no switch: the route
+ * comes from geometry alone, by the rule of chv_scale_lanczos_to_420 with tap strides of 2 bytes (luma, y420p10 chroma) and 4 bytes (P010
+ * chroma).  Launches: one per route per chunk, at most two per chunk, counted by "lanczos_hbd_launches" (chv_debug_get_counter; process-wide).
+ * A chunk is CHV_420_LADDER_CHUNK(n_rungs, dst_planes, src_planes) pictures.  A longer list is split along the PICTURES. */
+int chv_scale_lanczos_hbd_to_420(chv_context *ctx, const chv_image *dst, const chv_image *src);
+int chv_scale_lanczos_hbd_to_420_ladder(chv_context *ctx, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n);
 /* Lanczos-3 resize of one NV12 or y420p picture INTO a BGRA or RGBA plane of `dst`'s size, in one launch: the decoder side's rendition
  * (DESIGN.md section 4.4.6).  The logical planes Y, Cb and Cr of `src` (NV12: Cb and Cr are components 0 and 1 of plane 1; y420p: planes 1
  * and 2) are each resampled to dst's w x h exactly as chv_scale_lanczos resamples a 1-component plane — the chroma planes straight from

@@ -228,6 +228,9 @@ private func pixelFormatCode(_ fmt: PixelFormat) -> Int {
     case .y444p: return Int(CHV_FMT_Y444P.rawValue)
     case .RGBA: return Int(CHV_FMT_RGBA.rawValue)
     case .BGRA: return Int(CHV_FMT_BGRA.rawValue)
+    // (10-bit 4:2:0: the two cases INTEGRATION.md adds to `enum PixelFormat`, sample.pict.swift:19 "TODO: Higher bit-depth formats")
+    case .p010: return Int(CHV_FMT_P010.rawValue)
+    case .y420p10: return Int(CHV_FMT_Y420P10.rawValue)
     default: return Int(CHV_FMT_INVALID.rawValue)
     }
 }
@@ -774,6 +777,16 @@ func decoderFramePlanes(_ format: PixelFormat, size: Vector2, strides: [Int]? = 
         planes = [Plane(size: size, stride: w, bitDepth: 8, components: [.y]),
                   Plane(size: size, stride: w, bitDepth: 8, components: [.cb]),
                   Plane(size: size, stride: w, bitDepth: 8, components: [.cr])]
+    // 10-bit frames: a sample is a little-endian 16-bit word and a component one BYTE of a texel, as for the packed 4:2:2 formats
+    case .p010:
+        let c = Vector2(Float(max(w / 2, 1)), Float(max(h / 2, 1)))
+        planes = [Plane(size: size, stride: 2 * w, bitDepth: 10, components: [.y, .y]),
+                  Plane(size: c, stride: 4 * Int(c.x), bitDepth: 10, components: [.cb, .cb, .cr, .cr])]
+    case .y420p10:
+        let c = Vector2(Float(max(w / 2, 1)), Float(max(h / 2, 1)))
+        planes = [Plane(size: size, stride: 2 * w, bitDepth: 10, components: [.y, .y]),
+                  Plane(size: c, stride: 2 * Int(c.x), bitDepth: 10, components: [.cb, .cb]),
+                  Plane(size: c, stride: 2 * Int(c.x), bitDepth: 10, components: [.cr, .cr])]
     default:
         throw ComputeError.badInputData(description: "Invalid pixel format")
     }
@@ -823,6 +836,43 @@ func scaleLanczosTo420(_ context: ComputeContext, srcs: [PictureSample], rungs: 
         }
     }
     try check(chv_scale_lanczos_to_420_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
+    return context
+}
+
+/// Lanczos-3 from a 10-bit decoder picture (p010 or y420p10) into an 8-bit nv12 or y420p picture (chv_scale_lanczos_hbd_to_420, DESIGN.md
+/// section 4.4.10): the logical images Y, Cb and Cr resampled one by one on their 10-bit codes, the result divided by four (exactly) before
+/// its one rounding; no dither, no colour arithmetic, no re-siting.
+func scaleLanczosHbdTo420(_ context: ComputeContext, src: PictureSample, target: PictureSample) throws -> ComputeContext {
+    guard let targetImage = target.imageBuffer(), var targetDesc = describe(targetImage, maxPlanes: 3) else {
+        throw ComputeError.badTarget
+    }
+    guard let image = src.imageBuffer(), var desc = describe(image, maxPlanes: 3) else {
+        throw ComputeError.badInputData(description: "Bad input image")
+    }
+    try check(chv_scale_lanczos_hbd_to_420(context.handle, &targetDesc, &desc))
+    return context
+}
+
+/// The ladder of it (chv_scale_lanczos_hbd_to_420_ladder): rungs[r][i] receives what scaleLanczosHbdTo420(context, src: srcs[i], target:
+/// rungs[r][i]) would write — one format and one size for all sources, nv12 or y420p for all targets.
+func scaleLanczosHbdTo420(_ context: ComputeContext, srcs: [PictureSample], rungs: [[PictureSample]]) throws -> ComputeContext {
+    var targets = [chv_image](), sources = [chv_image]()
+    for src in srcs {
+        guard let image = src.imageBuffer(), let desc = describe(image, maxPlanes: 3) else {
+            throw ComputeError.badInputData(description: "Bad input image")
+        }
+        sources.append(desc)
+    }
+    for rung in rungs {
+        guard rung.count == srcs.count else { throw ComputeError.invalidValue }
+        for target in rung {
+            guard let targetImage = target.imageBuffer(), let targetDesc = describe(targetImage, maxPlanes: 3) else {
+                throw ComputeError.badTarget
+            }
+            targets.append(targetDesc)
+        }
+    }
+    try check(chv_scale_lanczos_hbd_to_420_ladder(context.handle, &targets, Int32(rungs.count), &sources, Int32(srcs.count)))
     return context
 }
 #endif

@@ -34,6 +34,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                 convert420: Bool = false,
                 convertToRgb: Bool = false,
                 convertDecoderFormats: Bool = false,
+                convertHighBitDepth: Bool = false,
                 computeContext: ComputeContext? = nil) {
         self.clock = clock
         self.outputSize = outputSize
@@ -44,6 +45,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
         self.convert420 = convert420
         self.convertToRgb = convertToRgb
         self.convertDecoderFormats = convertDecoderFormats
+        self.convertHighBitDepth = convertHighBitDepth
         do {
             if let context = computeContext {
                 self.context = createComputeContext(sharing: context)
@@ -81,6 +83,10 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
                         let decoderIn = [PixelFormat.nv21, .y422p, .y444p, .yuvs, .zvuy].contains(src.pixelFormat())
                         if strongSelf.convertDecoderFormats && decoderIn && (format == .nv12 || format == .y420p) {
                             return try scaleLanczosTo420($0, src: src, target: dst)
+                        }
+                        let hbdIn = src.pixelFormat() == .p010 || src.pixelFormat() == .y420p10
+                        if strongSelf.convertHighBitDepth && hbdIn && (format == .nv12 || format == .y420p) {
+                            return try scaleLanczosHbdTo420($0, src: src, target: dst)
                         }
                         if strongSelf.convertToRgb && yuvIn && (format == .BGRA || format == .RGBA) {
                             return try scaleLanczosFromYuv($0, src: src, target: dst, colorspace: strongSelf.colorspace)
@@ -150,6 +156,7 @@ public class PictureFilter: Tx<PictureSample, PictureSample> {
     let convert420: Bool       // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
     let convertToRgb: Bool     // the Lanczos scaler takes nv12 / y420p -> BGRA / RGBA (off: the pair is an error, as it was)
     let convertDecoderFormats: Bool      // the Lanczos scaler takes nv21 / y422p / y444p / yuvs / zvuy -> nv12 / y420p (off: an error, as it was)
+    let convertHighBitDepth: Bool        // the Lanczos scaler takes p010 / y420p10 -> nv12 / y420p (off: an error, as it was)
     var context: ComputeContext?
 }
 #endif

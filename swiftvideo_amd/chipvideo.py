@@ -29,6 +29,7 @@ K_IMG_BGRA_NV12_INT, K_IMG_RGBA_NV12_INT, K_IMG_BGRA_Y420P_INT, K_IMG_RGBA_Y420P
 
 FMT_NV12, FMT_NV21, FMT_YUVS, FMT_ZVUY, FMT_Y420P, FMT_Y422P, FMT_Y444P, FMT_RGBA, FMT_BGRA = range(9)
 FMT_INVALID = 11
+FMT_P010, FMT_Y420P10 = 12, 13          # 10-bit 4:2:0: sources of chv_scale_lanczos_hbd_to_420 only
 CSC_BT601_LIMITED, CSC_BT709_LIMITED, CSC_BT601_FULL, CSC_BT709_FULL = range(4)
 MAX_LAYERS = 16
 
@@ -140,6 +141,8 @@ _SIGNATURES = {
     "chv_scale_lanczos_420_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
     "chv_scale_lanczos_to_420": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image)]),
     "chv_scale_lanczos_to_420_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
+    "chv_scale_lanczos_hbd_to_420": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image)]),
+    "chv_scale_lanczos_hbd_to_420_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int]),
     "chv_scale_lanczos_from_yuv": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.POINTER(KernelOpts)]),
     "chv_scale_lanczos_from_yuv_batch": (C.c_int, [C.c_void_p, C.POINTER(Image), C.POINTER(Image), C.c_int, C.POINTER(KernelOpts)]),
     "chv_scale_lanczos_from_yuv_ladder": (C.c_int, [C.c_void_p, C.POINTER(Image), C.c_int, C.POINTER(Image), C.c_int, C.POINTER(KernelOpts)]),

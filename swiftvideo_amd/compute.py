@@ -29,7 +29,7 @@ __all__ = [
     "destroyComputeContext", "beginComputePass", "endComputePass", "usingContext", "runComputeKernel",
     "applyComputeImage", "uploadComputePicture", "downloadComputePicture", "uploadComputeBuffer",
     "downloadComputeBuffer", "createPictureSample", "GPUBarrierUpload", "GPUBarrierDownload", "VideoMixer",
-    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosTo420", "scaleLanczosTo420Ladder", "LanczosTo420Ladder", "decoderFramePlanes", "pictureFromDecoderFrame", "DECODER_FORMATS", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "scaleLanczosRgbLadder", "LanczosRgbLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
+    "compositeTick", "scaleLanczos", "LanczosBatch", "scaleLanczosToYuv", "LanczosToYuvBatch", "scaleLanczosToYuvLadder", "LanczosToYuvLadder", "scaleLanczosLadder", "LanczosLadder", "scaleLanczos420", "scaleLanczos420Ladder", "Lanczos420Ladder", "scaleLanczosTo420", "scaleLanczosTo420Ladder", "LanczosTo420Ladder", "decoderFramePlanes", "pictureFromDecoderFrame", "DECODER_FORMATS", "HIGH_BIT_DEPTH_FORMATS", "scaleLanczosHbdTo420", "scaleLanczosHbdTo420Ladder", "LanczosHbdTo420Ladder", "scaleLanczosFromYuv", "scaleLanczosFromYuvBatch", "LanczosFromYuvBatch", "scaleLanczosFromYuvLadder", "LanczosFromYuvLadder", "scaleLanczosRgbLadder", "LanczosRgbLadder", "PictureFilter", "CustomKernel", "buildComputeKernel", "TickBatch", "VideoMixerGroup", "BufferImage",
 ]
 
 
@@ -82,6 +82,8 @@ class PixelFormat(enum.IntEnum):
     RGBA = cv.FMT_RGBA
     BGRA = cv.FMT_BGRA
     invalid = cv.FMT_INVALID
+    p010 = cv.FMT_P010            # 10-bit 4:2:0, no reference counterpart (sample.pict.swift:19): Y plane + CbCr plane of 16-bit words, code = word >> 6
+    y420p10 = cv.FMT_Y420P10      # FFmpeg's yuv420p10le: three planes of 16-bit words, code = word & 1023
 
 
 # ---- devices / contexts ---------------------------------------------------------
@@ -218,10 +220,13 @@ def planesForFormat(fmt, size):
 
 
 DECODER_FORMATS = (PixelFormat.nv21, PixelFormat.yuvs, PixelFormat.zvuy, PixelFormat.y422p, PixelFormat.y444p)
+# the 10-bit frames a decoder makes (HEVC Main10, AV1 10-bit): what scaleLanczosHbdTo420 takes and nothing else does
+HIGH_BIT_DEPTH_FORMATS = (PixelFormat.p010, PixelFormat.y420p10)
 
 
 def decoderFramePlanes(fmt, size, strides=None):
-    """The planes of a decoder frame of one of the five formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p), as
+    """The planes of a decoder frame of one of the seven formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p; p010 and
+    y420p10 of HIGH_BIT_DEPTH_FORMATS, whose planes hold 16-bit words: rows of 2 (p010 chroma: 4) bytes per texel, even strides), as
     framePlanes / planeSize describe them (dec.video.ffmpeg.swift:162-185): plane sizes as there, strides from `strides` (the frame's
     linesize array; packed rows when None).  A packed 4:2:2 plane is the picture's width x height with two bytes per pixel — yuvs: Y0 Cb Y1 Cr,
     zvuy: Cb Y0 Cr Y1, FFmpeg's YUYV422 / UYVY422 — which is what chv_scale_lanczos_to_420 takes (include/chipvideo.h)."""
@@ -236,6 +241,13 @@ def decoderFramePlanes(fmt, size, strides=None):
         planes = [Plane((w, h), w, 8, ["y"]), Plane((w // 2, h), w // 2, 8, ["cb"]), Plane((w // 2, h), w // 2, 8, ["cr"])]
     elif fmt == PixelFormat.y444p:
         planes = [Plane((w, h), w, 8, ["y"]), Plane((w, h), w, 8, ["cb"]), Plane((w, h), w, 8, ["cr"])]
+    elif fmt == PixelFormat.p010:
+        # (a component is a BYTE of a texel, as for the packed 4:2:2 formats: a sample is a little-endian 16-bit word)
+        cw, ch = max(1, w // 2), max(1, h // 2)
+        planes = [Plane((w, h), 2 * w, 10, ["y", "y.hi"]), Plane((cw, ch), 4 * cw, 10, ["cb", "cb.hi", "cr", "cr.hi"])]
+    elif fmt == PixelFormat.y420p10:
+        cw, ch = max(1, w // 2), max(1, h // 2)
+        planes = [Plane((w, h), 2 * w, 10, ["y", "y.hi"]), Plane((cw, ch), 2 * cw, 10, ["cb", "cb.hi"]), Plane((cw, ch), 2 * cw, 10, ["cr", "cr.hi"])]
     else:
         raise ComputeError(5, "Invalid pixel format")
     if strides is not None:
@@ -249,8 +261,8 @@ def decoderFramePlanes(fmt, size, strides=None):
 
 
 def pictureFromDecoderFrame(fmt, size, arrays, strides=None, **kw):
-    """A CPU PictureSample over the plane arrays of a decoder frame of one of DECODER_FORMATS (decoderFramePlanes says how they are shaped;
-    `arrays[i]` holds rows of strides[i] bytes).  uploadComputePicture and downloadComputePicture carry it like any other picture."""
+    """A CPU PictureSample over the plane arrays of a decoder frame of one of DECODER_FORMATS or HIGH_BIT_DEPTH_FORMATS (decoderFramePlanes
+    says how they are shaped; `arrays[i]` holds rows of strides[i] BYTES — a plane of 16-bit words is passed as its bytes, .view(np.uint8)).  uploadComputePicture and downloadComputePicture carry it like any other picture."""
     planes = decoderFramePlanes(fmt, size, strides)
     bufs = []
     for p, a in zip(planes, arrays):
@@ -947,6 +959,34 @@ def scaleLanczosTo420Ladder(ctx, rungs, srcs):
     return LanczosTo420Ladder(rungs, srcs).run(ctx)
 
 
+def scaleLanczosHbdTo420(ctx, dst, src):
+    """Lanczos-3 resize of a 10-bit decoder picture (p010 or y420p10) into an 8-bit nv12 or y420p picture (chv_scale_lanczos_hbd_to_420,
+    DESIGN.md section 4.4.10): the logical images Y, Cb and Cr resampled one by one on their 10-bit codes as scaleLanczos resamples a
+    1-component plane, the result divided by four (exactly) before its one rounding — no dither, no colour arithmetic, no re-siting."""
+    d, s = _image_desc(dst), _image_desc(src)
+    if d is None:
+        raise ComputeError(4, "target has no GPU image buffer")
+    if s is None:
+        raise ComputeError(5, "Bad input image")
+    cv.check(cv.load().chv_scale_lanczos_hbd_to_420(ctx.handle, C.byref(d), C.byref(s)))
+    return ctx
+
+
+class LanczosHbdTo420Ladder(LanczosLadder):
+    """LanczosLadder whose sources are p010 or y420p10 pictures (chv_scale_lanczos_hbd_to_420_ladder): one format
+    for all sources, nv12 or y420p for all targets; one launch per route per chunk, the bytes of the single scaleLanczosHbdTo420 calls."""
+
+    def run(self, ctx):
+        cv.check(cv.load().chv_scale_lanczos_hbd_to_420_ladder(ctx.handle, self._d, self.n_rungs, self._s, self.n))
+        return ctx
+
+
+def scaleLanczosHbdTo420Ladder(ctx, rungs, srcs):
+    """Every nv12 or y420p rendition of one or several 10-bit pictures of one size and one format (chv_scale_lanczos_hbd_to_420_ladder):
+    rungs[r][i] receives what scaleLanczosHbdTo420(ctx, rungs[r][i], srcs[i]) would write."""
+    return LanczosHbdTo420Ladder(rungs, srcs).run(ctx)
+
+
 # ---- pipeline operators -----------------------------------------------------------------------
 def scaleLanczosFromYuv(ctx, dst, src, colorspace=cv.CSC_BT601_LIMITED):
     """Lanczos-3 resize of the nv12 or y420p picture `src` into one BGRA or RGBA plane `dst`, in one launch (chv_scale_lanczos_from_yuv,
@@ -1055,7 +1095,8 @@ class PictureFilter:
     pair the kernel table has), or a separable Lanczos-3 resample (`scaler="lanczos"`: BGRA -> BGRA, nv12 -> nv12 or y420p -> y420p
     without a conversion, a 4:2:0 picture plane by plane; BGRA or RGBA -> nv12 or y420p through the integer matrix, scaleLanczosToYuv;
     with `convert420=True` also nv12 <-> y420p, scaleLanczos420, with `convertDecoderFormats=True` also nv21, y422p, y444p, yuvs or zvuy
-    -> nv12 or y420p, scaleLanczosTo420, and with `convertToRgb=True` also nv12 or y420p -> BGRA or RGBA through the
+    -> nv12 or y420p, scaleLanczosTo420, with `convertHighBitDepth=True` also p010 or y420p10 -> nv12 or y420p, scaleLanczosHbdTo420, and
+    with `convertToRgb=True` also nv12 or y420p -> BGRA or RGBA through the
     integer matrix, scaleLanczosFromYuv — both off by default: a host that did not ask for a conversion gets the error it got).
     CPU samples are uploaded first; the sample's time stamps, ids and transform state are carried over.
     Results land in a ring of `numberBackingImages` device images like the mixer's (mix.video.swift:148-167)."""
@@ -1063,12 +1104,14 @@ class PictureFilter:
     numberBackingImages = 10
 
     def __init__(self, outputSize, outputFormat=PixelFormat.BGRA, computeContext=None, scaler="bilinear",
-                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False, convertToRgb=False, convertDecoderFormats=False):
+                 colorspace=cv.CSC_BT601_LIMITED, integerMatrix=True, convert420=False, convertToRgb=False, convertDecoderFormats=False,
+                 convertHighBitDepth=False):
         """integerMatrix: an RGB picture converted to a 4:2:0 format goes through the integer BT.601/709 matrix of `colorspace`
         (img_*_int, DESIGN.md 4.5: what an encoder expects); False selects the reference's own float kernels (img_bgra_nv12 ...,
         full range, kernels.cl.swift:96-99)."""
         self.integerMatrix, self.convert420, self.convertToRgb = integerMatrix, convert420, convertToRgb
         self.convertDecoderFormats = convertDecoderFormats
+        self.convertHighBitDepth = convertHighBitDepth
         if scaler not in ("bilinear", "lanczos"):
             raise ComputeError(0, f"unknown scaler {scaler!r}")
         try:
@@ -1116,6 +1159,9 @@ class PictureFilter:
             elif self.scaler == "lanczos" and self.convertDecoderFormats and src.pixelFormat() in DECODER_FORMATS \
                     and self.outputFormat in (PixelFormat.nv12, PixelFormat.y420p):
                 scaleLanczosTo420(ctx, dst, src)
+            elif self.scaler == "lanczos" and self.convertHighBitDepth and src.pixelFormat() in HIGH_BIT_DEPTH_FORMATS \
+                    and self.outputFormat in (PixelFormat.nv12, PixelFormat.y420p):
+                scaleLanczosHbdTo420(ctx, dst, src)
             elif self.scaler == "lanczos" and self.convertToRgb and src.pixelFormat() in (PixelFormat.nv12, PixelFormat.y420p) \
                     and self.outputFormat in (PixelFormat.BGRA, PixelFormat.RGBA):
                 scaleLanczosFromYuv(ctx, dst, src, self.colorspace)

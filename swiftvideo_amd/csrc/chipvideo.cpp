@@ -33,6 +33,7 @@
 #include "lanczos_planar_ladder.h"
 #include "lanczos_420.h"
 #include "lanczos_to_420.h"
+#include "lanczos_hbd.h"
 #include "lanczos_from_yuv.h"
 #include "lanczos_from_yuv_ladder.h"
 #include "lanczos_rgb_ladder.h"
@@ -133,6 +134,9 @@ void chv::register_lanczos_420_launcher(Lanczos420Launcher fn) { g_lanczos_420_l
 // and for the five other decoder formats of chv_scale_lanczos_to_420 / chv_scale_lanczos_to_420_ladder (lanczos_to_420.h, kernels_lanczos_to_420.hip.cpp)
 static std::atomic<LanczosTo420Launcher> g_lanczos_to_420_launcher{nullptr};
 void chv::register_lanczos_to_420_launcher(LanczosTo420Launcher fn) { g_lanczos_to_420_launcher.store(fn, std::memory_order_release); }
+// and for the 10-bit sources of chv_scale_lanczos_hbd_to_420 / chv_scale_lanczos_hbd_to_420_ladder (lanczos_hbd.h, kernels_lanczos_hbd.hip.cpp)
+static std::atomic<LanczosHbdLauncher> g_lanczos_hbd_launcher{nullptr};
+void chv::register_lanczos_hbd_launcher(LanczosHbdLauncher fn) { g_lanczos_hbd_launcher.store(fn, std::memory_order_release); }
 // and for chv_scale_lanczos_from_yuv / chv_scale_lanczos_from_yuv_batch (lanczos_from_yuv.h, kernels_lanczos_from_yuv.hip.cpp)
 static std::atomic<LanczosFromYuvLauncher> g_lanczos_from_yuv_launcher{nullptr};
 void chv::register_lanczos_from_yuv_launcher(LanczosFromYuvLauncher fn) { g_lanczos_from_yuv_launcher.store(fn, std::memory_order_release); }
@@ -167,6 +171,7 @@ extern "C" int chv_debug_get_counter(const char *name, unsigned long long *value
     if (!strcmp(name, "lanczos_planar_ladder_launches")) { *value = debug_counters().lanczos_planar_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_420_ladder_launches")) { *value = debug_counters().lanczos_420_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_to_420_launches")) { *value = debug_counters().lanczos_to_420_launches.load(std::memory_order_relaxed); return CHV_OK; }
+    if (!strcmp(name, "lanczos_hbd_launches")) { *value = debug_counters().lanczos_hbd_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_launches")) { *value = debug_counters().lanczos_from_yuv_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_from_yuv_ladder_launches")) { *value = debug_counters().lanczos_from_yuv_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
     if (!strcmp(name, "lanczos_rgb_ladder_launches")) { *value = debug_counters().lanczos_rgb_ladder_launches.load(std::memory_order_relaxed); return CHV_OK; }
@@ -1000,7 +1005,8 @@ static int wait_for_uploads(hipStream_t stream, std::vector<BatchDep> &deps) {
     return CHV_OK;
 }
 
-static int plane_to_device(const chv_plane &p, int comps, int device, DPlane *out, int err, const char *what, int idx) {
+// align: what the plane's start address and pitch must be a multiple of; 0: the rule of every 8-bit format (4 for a 4-component plane)
+static int plane_to_device(const chv_plane &p, int comps, int device, DPlane *out, int err, const char *what, int idx, int align = 0) {
     if (!buf_ok(p.buffer)) return fail(err, "%s plane %d: no device buffer", what, idx);
     if (p.buffer->device != device) return fail(err, "%s plane %d lives on device %d, context on %d", what, idx, p.buffer->device, device);
     if (p.width <= 0 || p.height <= 0) return fail(err, "%s plane %d: size %dx%d", what, idx, p.width, p.height);
@@ -1013,8 +1019,10 @@ static int plane_to_device(const chv_plane &p, int comps, int device, DPlane *ou
         __builtin_add_overflow(end, p.offset, &end))
         return fail(err, "%s plane %d: extent overflows", what, idx);
     if (end > p.buffer->size) return fail(err, "%s plane %d: extent %zu exceeds buffer size %zu", what, idx, end, p.buffer->size);
-    if (comps == 4 && (((uintptr_t)p.buffer->ptr + p.offset) & 3 || (p.pitch & 3)))
+    if (!align && comps == 4 && (((uintptr_t)p.buffer->ptr + p.offset) & 3 || (p.pitch & 3)))
         return fail(err, "%s plane %d: 4-component planes must be 4-byte aligned", what, idx);
+    if (align && ((((uintptr_t)p.buffer->ptr + p.offset) | (uintptr_t)p.pitch) & (uintptr_t)(align - 1)))
+        return fail(err, "%s plane %d: start and pitch must be multiples of %d", what, idx, align);
     out->ptr = (uint8_t *)p.buffer->ptr + p.offset;
     out->w = p.width; out->h = p.height; out->pitch = p.pitch; out->comps = comps;
     if (g_deps) g_deps->push_back(p.buffer);
@@ -2898,6 +2906,89 @@ extern "C" int chv_scale_lanczos_to_420(chv_context *c, const chv_image *dst, co
     if (!src) return fail(CHV_ERR_BAD_INPUT, "Lanczos to 4:2:0: null source");
     // an NV12 or y420p source is chv_scale_lanczos_420's; everything else is the ladder of one rung and one picture
     return lanczos_planar_planes(src) ? chv_scale_lanczos_420(c, dst, src) : chv_scale_lanczos_to_420_ladder(c, dst, 1, src, 1);
+}
+
+// ---- chv_scale_lanczos_hbd_to_420 / chv_scale_lanczos_hbd_to_420_ladder: P010, y420p10 -> NV12 / y420p ----
+// planes of a source of one of the two 10-bit formats, 0 for every other (format, structure); *kind: LanczosHbdSource
+static int lanczos_hbd_kind(const chv_image *img, int *kind) {
+    if (!img) return 0;
+    switch (img->format) {
+    case CHV_FMT_P010: *kind = kHbdP010; return img->n_planes == 2 ? 2 : 0;
+    case CHV_FMT_Y420P10: *kind = kHbdPlanar; return img->n_planes == 3 ? 3 : 0;
+    default: return 0;
+    }
+}
+
+// every plane of one 10-bit source -> out[0 .. np), every check of plane_to_device on every plane with components = bytes per texel (2; 4 for
+// P010's CbCr); a 16-bit plane starts at an even address with an even pitch; Cb and Cr must agree
+static int lanczos_hbd_planes(chv_context *c, const chv_image *img, int np, int kind, int idx, DPlane *out) {
+    int k2 = 0;
+    if (lanczos_hbd_kind(img, &k2) != np || k2 != kind)
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos 10-bit to 4:2:0: source %d must be p010 (2 planes) or y420p10 (3 planes)", idx);
+    for (int p = 0; p < np; p++) {
+        int rc = plane_to_device(img->planes[p], kind == kHbdP010 && p ? 4 : 2, c->device, &out[p], CHV_ERR_BAD_INPUT, "input", p, 2);
+        if (rc) return rc;
+    }
+    if (np == 3 && (out[1].w != out[2].w || out[1].h != out[2].h))
+        return fail(CHV_ERR_BAD_INPUT, "Lanczos 10-bit to 4:2:0: source %d: chroma planes of %dx%d and %dx%d (Cb and Cr have one size)", idx, out[1].w, out[1].h, out[2].w, out[2].h);
+    return CHV_OK;
+}
+
+extern "C" int chv_scale_lanczos_hbd_to_420_ladder(chv_context *c, const chv_image *dsts, int n_rungs, const chv_image *srcs, int n) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    bool empty;
+    int rc = lanczos_ladder_header(dsts, n_rungs, srcs, n, &empty);
+    if (rc || empty) return rc;
+    const LanczosHbdLauncher launcher = g_lanczos_hbd_launcher.load(std::memory_order_acquire);
+    const int dnp = lanczos_planar_planes(&dsts[0]);
+    if (!dnp) return fail(CHV_ERR_BAD_TARGET, "Lanczos 10-bit to 4:2:0: target 0 must be nv12 with 2 planes or y420p with 3");
+    int kind = 0;
+    const int snp = lanczos_hbd_kind(&srcs[0], &kind);
+    if (!snp) return fail(CHV_ERR_BAD_INPUT, "Lanczos 10-bit to 4:2:0: source 0 must be p010 (2 planes) or y420p10 (3 planes)");
+    rc = lanczos_ladder_formats(dsts, n_rungs, srcs, n);
+    if (rc) return rc;
+    // a picture's record: the dnp target planes of rung 0, of rung 1, ..., then the snp source planes
+    const size_t per = (size_t)n_rungs * dnp + snp, src_at = (size_t)n_rungs * dnp;
+    std::vector<DPlane> planes(per * n);
+    DepScope deps;
+    for (int i = 0; i < n; i++) {
+        DPlane *pi = planes.data() + per * i;
+        rc = lanczos_420_targets(c, dsts, n_rungs, n, i, dnp, pi, planes.data());
+        if (rc) return rc;
+        rc = lanczos_hbd_planes(c, &srcs[i], snp, kind, i, pi + src_at);
+        if (rc) return rc;
+        rc = lanczos_one_source_size(pi + src_at, planes.data() + src_at, snp, i);
+        if (rc) return rc;
+    }
+    const DPlane *s0 = planes.data() + src_at;
+    rc = lanczos_begin(c, deps, launcher ? CHV_OK : fail(CHV_ERR_NOT_IMPLEMENTED, "this build has no 10-bit Lanczos kernels"));
+    if (rc) return rc;
+    // two tables per logical image per rung
+    LanczosRef refs[2 * kLanczosPlanarMaxPlanes * CHV_LADDER_MAX_RUNGS];
+    LanczosHbdJob job;
+    memset(&job, 0, sizeof job);
+    job.n_rungs = n_rungs; job.source = kind; job.dst_planes = dnp; job.src_planes = snp;
+    job.luma_w = s0[0].w; job.luma_h = s0[0].h;
+    job.chroma_w = s0[1].w; job.chroma_h = s0[1].h;
+    rc = lanczos_420_tables(c, planes.data(), n_rungs, dnp, refs, &job);
+    if (rc) return rc;
+    return lanczos_send(c, planes.data(), per, n, lanczos_chunk(per), [&](DPlane *dev, int m) {
+        job.batch = dev; job.n_pictures = m;
+        int launches = 0;
+        hipError_t e = launcher(job, c->stream, &launches);
+        debug_counters().lanczos_hbd_launches.fetch_add((unsigned long long)launches, std::memory_order_relaxed);
+        return e != hipSuccess ? hip_fail(e, "lanczos 10-bit launch") : CHV_OK;
+    });
+}
+
+extern "C" int chv_scale_lanczos_hbd_to_420(chv_context *c, const chv_image *dst, const chv_image *src) {
+    if (!ctx_ok(c)) return fail(CHV_ERR_INVALID_CONTEXT, "bad context");
+    FLUSH_PENDING(c);
+    if (!lanczos_planar_planes(dst)) return fail(CHV_ERR_BAD_TARGET, "Lanczos 10-bit to 4:2:0: the target must be nv12 with 2 planes or y420p with 3");
+    if (!src) return fail(CHV_ERR_BAD_INPUT, "Lanczos 10-bit to 4:2:0: null source");
+    // the ladder of one rung and one picture
+    return chv_scale_lanczos_hbd_to_420_ladder(c, dst, 1, src, 1);
 }
 
 // ---- chv_scale_lanczos_from_yuv: an NV12 or y420p picture -> one BGRA / RGBA plane ----

@@ -1,6 +1,6 @@
 // lanczos_strip_core.hip.h — THE wave-per-strip row code of the planar Lanczos-3 resamplers: one body, strip_core,
 // for a strip of one logical plane.  planar_strip (lanczos_planar_body.hip.h), x420_strip (lanczos_420_body.hip.h), to420_strip
-// (lanczos_to_420_body.hip.h) and fy_strip (lanczos_from_yuv_body.hip.h) are wrappers of a few lines: each states how its lanes map to source
+// (lanczos_to_420_body.hip.h), hbd_strip (lanczos_hbd_body.hip.h) and fy_strip (lanczos_from_yuv_body.hip.h) are wrappers of a few lines: each states how its lanes map to source
 // bytes (a column description) and where a finished value goes (a sink).
 //
 // The body sees the target as rows of BYTE columns: output byte b of a row belongs to texel b / OC, and its taps are SS bytes apart in the
@@ -23,11 +23,22 @@ namespace chv {
 //         bytes) and the tap extraction (SS 1, 2: dwords realigned so that tap 0 is byte 0, taps in 8- or 16-bit fields; SS 4: one dword per tap).
 //   OC    target bytes per texel, 1 or 2: output byte xe is texel xe / OC, component xe % OC.
 //   TWO   the ring slot holds one staged row of EACH of two source planes (g.src, then src2: same size, own start and pitch).
-template <int SS_, int OC_, bool TWO_ = false> struct StripCols {
+//   WIDE  what a sample is.  kSampleByte: one byte.  kSampleHigh10, kSampleLow10 (SS 2 or 4, even offsets): the little-endian 16-bit word that
+//         starts at the tap's byte — the whole field the byte extraction masks to its low byte — as the 10-bit code word >> 6 or word & 1023
+//         (DESIGN.md section 4.4.10).  Staging, edge replication, the byte gather and the dwords a lane reads are the byte samples'.
+enum StripSample : int { kSampleByte = 0, kSampleHigh10 = 1, kSampleLow10 = 2 };
+template <int SS_, int OC_, bool TWO_ = false, int WIDE_ = kSampleByte> struct StripCols {
     static_assert((SS_ == 1 || SS_ == 2 || SS_ == 4) && (OC_ == 1 || OC_ == 2), "tap stride 1, 2 or 4 bytes, 1 or 2 target components");
-    static constexpr int SS = SS_, OC = OC_;
+    static_assert(WIDE_ == kSampleByte || ((WIDE_ == kSampleHigh10 || WIDE_ == kSampleLow10) && SS_ >= 2), "a 16-bit sample needs a tap stride of 2 or 4");
+    static constexpr int SS = SS_, OC = OC_, WIDE = WIDE_;
     static constexpr bool TWO = TWO_;
 };
+// the sample of a tap from the dword shifted so that the tap's first byte is bit 0
+template <int WIDE> CHV_DEV uint32_t strip_sample(uint32_t field) {
+    if constexpr (WIDE == kSampleHigh10) return (field & 0xffffu) >> 6;
+    else if constexpr (WIDE == kSampleLow10) return field & 1023u;
+    else return field & 255u;
+}
 
 // The sink of the bodies that store bytes: the lane's code at its byte of the quad's dword, then the quad's four bytes in every lane of it (two
 // quad-permute DPP moves) and a dword store per quad wherever the target allows it: plane start and pitch 4-byte aligned (uniform), quad
@@ -69,7 +80,7 @@ constexpr int PS_PRE = 2;            // (gathered rows) source rows in flight (r
 // there until the first real tap) — window indices stay static whatever the plane's tap counts are.
 template <int T, typename Cols, typename Open>
 CHV_DEV bool strip_core(const PlanarPlane &g, const DPlane &src2, int off0, int off1, int strip, int chunk, int rows_per_wave, uint8_t *lsm, Open &&open) {
-    constexpr int SS = Cols::SS, OC = Cols::OC;
+    constexpr int SS = Cols::SS, OC = Cols::OC, WIDE = Cols::WIDE;
     constexpr bool TWO = Cols::TWO;
     // dwords a lane reads from its first tap's dword on: taps at byte offsets o + k * SS, o = 0..3, k < T (SS == 4: one per tap)
     constexpr int ND = (T * SS - SS + 7) / 4, NA = ND - 1;
@@ -197,7 +208,7 @@ CHV_DEV bool strip_core(const PlanarPlane &g, const DPlane &src2, int off0, int 
             float acc = 0.f;
             if constexpr (SS == 4) {                               // tap k is byte sh of dword k
 #pragma unroll
-                for (int k = 0; k < T; k++) acc = __builtin_fmaf(wr[k], (float)((raw[k] >> (8 * sh)) & 255u), acc);
+                for (int k = 0; k < T; k++) acc = __builtin_fmaf(wr[k], (float)strip_sample<WIDE>(raw[k] >> (8 * sh)), acc);
             } else {                                               // shifted so that tap 0 is byte 0
                 uint32_t al[NA];
 #pragma unroll
@@ -205,7 +216,7 @@ CHV_DEV bool strip_core(const PlanarPlane &g, const DPlane &src2, int off0, int 
 #pragma unroll
                 for (int k = 0; k < T; k++) {
                     const uint32_t word = SS == 2 ? al[k >> 1] : al[k >> 2];
-                    const uint32_t byte = SS == 2 ? (word >> (16 * (k & 1))) & 255u : (word >> (8 * (k & 3))) & 255u;
+                    const uint32_t byte = strip_sample<WIDE>(SS == 2 ? word >> (16 * (k & 1)) : word >> (8 * (k & 3)));
                     acc = __builtin_fmaf(wr[k], (float)byte, acc);
                 }
             }

@@ -1,6 +1,6 @@
 // lanczos_strip_parts.hip.h — what every wave-per-strip Lanczos-3 body is built from: lanczos3_strip<T>
 // (kernels_lanczos.hip.cpp), lanczos_yuv_strip_body (lanczos_to_yuv_body.hip.h), rgb_strip<T> (lanczos_rgb_body.hip.h) and strip_core
-// (lanczos_strip_core.hip.h, the body of planar_strip, x420_strip, to420_strip and fy_strip).  The bodies differ in their windows and in
+// (lanczos_strip_core.hip.h, the body of planar_strip, x420_strip, to420_strip, hbd_strip and fy_strip).  The bodies differ in their windows and in
 // where a finished row goes; these pieces they spell alike.
 #pragma once
 #include "pixel_math.hip.h"

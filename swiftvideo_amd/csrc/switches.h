@@ -59,6 +59,7 @@ struct DebugCounters {
     std::atomic<unsigned long long> lanczos_planar_ladder_launches{0};      // device launches made by chv_scale_lanczos_ladder
     std::atomic<unsigned long long> lanczos_420_ladder_launches{0};         // device launches made by the cross-format path of chv_scale_lanczos_420 / _420_ladder
     std::atomic<unsigned long long> lanczos_to_420_launches{0};             // device launches made by chv_scale_lanczos_to_420 / _to_420_ladder for the five formats they do not forward
+    std::atomic<unsigned long long> lanczos_hbd_launches{0};                // device launches made by chv_scale_lanczos_hbd_to_420 / _hbd_to_420_ladder
     std::atomic<unsigned long long> lanczos_from_yuv_launches{0};           // device launches made by chv_scale_lanczos_from_yuv / _from_yuv_batch
     std::atomic<unsigned long long> lanczos_from_yuv_ladder_launches{0};    // device launches made by chv_scale_lanczos_from_yuv_ladder
     std::atomic<unsigned long long> lanczos_rgb_ladder_launches{0};         // device launches made by chv_scale_lanczos_rgb_ladder

@@ -74,13 +74,15 @@ inline ComputeKernel defaultComputeKernelFromString(const std::string &str) {
 // ---- pixel formats and planes (sample.pict.swift:20-58) --------------------------------------
 enum class PixelFormat : int {
     nv12 = CHV_FMT_NV12, nv21 = CHV_FMT_NV21, yuvs = CHV_FMT_YUVS, zvuy = CHV_FMT_ZVUY, y420p = CHV_FMT_Y420P,
-    y422p = CHV_FMT_Y422P, y444p = CHV_FMT_Y444P, RGBA = CHV_FMT_RGBA, BGRA = CHV_FMT_BGRA, invalid = CHV_FMT_INVALID
+    y422p = CHV_FMT_Y422P, y444p = CHV_FMT_Y444P, RGBA = CHV_FMT_RGBA, BGRA = CHV_FMT_BGRA, invalid = CHV_FMT_INVALID,
+    p010 = CHV_FMT_P010, y420p10 = CHV_FMT_Y420P10      // 10-bit 4:2:0 (no reference counterpart): sources of scaleLanczosHbdTo420 only
 };
 inline std::string lowercasedName(PixelFormat f) {        // String(describing:).lowercased(), mix.video.swift:143-144
     switch (f) {
     case PixelFormat::nv12: return "nv12"; case PixelFormat::nv21: return "nv21"; case PixelFormat::yuvs: return "yuvs";
     case PixelFormat::zvuy: return "zvuy"; case PixelFormat::y420p: return "y420p"; case PixelFormat::y422p: return "y422p";
     case PixelFormat::y444p: return "y444p"; case PixelFormat::RGBA: return "rgba"; case PixelFormat::BGRA: return "bgra";
+    case PixelFormat::p010: return "p010"; case PixelFormat::y420p10: return "y420p10";
     default: return "invalid";
     }
 }
@@ -243,7 +245,8 @@ inline std::vector<Plane> planesForFormat(PixelFormat f, Vector2 size) {
     }
 }
 
-// The planes of a decoder frame of one of the five formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p), as framePlanes /
+// The planes of a decoder frame of one of the seven formats planesForFormat does not know (nv21, yuvs, zvuy, y422p, y444p; p010 and y420p10,
+// whose planes hold 16-bit words: 2 bytes per texel, 4 for p010's CbCr, even strides — what chv_scale_lanczos_hbd_to_420 takes), as framePlanes /
 // planeSize describe them (dec.video.ffmpeg.swift:162-185): plane sizes as there, strides from the frame's linesize array (packed rows when
 // null).  A packed 4:2:2 plane is the picture's width x height at two bytes per pixel (yuvs: Y0 Cb Y1 Cr, zvuy: Cb Y0 Cr Y1), which is what
 // chv_scale_lanczos_to_420 takes.
@@ -251,11 +254,15 @@ inline std::vector<Plane> decoderFramePlanes(PixelFormat f, Vector2 size, const 
     const int w = (int)size.x, h = (int)size.y;
     std::vector<Plane> planes;
     const Vector2 half{ (float)(w / 2), (float)(h / 2) }, halfw{ (float)(w / 2), (float)h };
+    const Vector2 half10{ (float)std::max(w / 2, 1), (float)std::max(h / 2, 1) };
     switch (f) {
     case PixelFormat::nv21: planes = { Plane{ size, w, 8, 1 }, Plane{ half, w / 2 * 2, 8, 2 } }; break;
     case PixelFormat::yuvs: case PixelFormat::zvuy: planes = { Plane{ size, 2 * w, 8, 2 } }; break;
     case PixelFormat::y422p: planes = { Plane{ size, w, 8, 1 }, Plane{ halfw, w / 2, 8, 1 }, Plane{ halfw, w / 2, 8, 1 } }; break;
     case PixelFormat::y444p: planes = { Plane{ size, w, 8, 1 }, Plane{ size, w, 8, 1 }, Plane{ size, w, 8, 1 } }; break;
+    // 10-bit frames: a sample is a little-endian 16-bit word and `components` the BYTES of a texel, as for the packed 4:2:2 formats
+    case PixelFormat::p010: planes = { Plane{ size, 2 * w, 10, 2 }, Plane{ half10, 4 * (int)half10.x, 10, 4 } }; break;
+    case PixelFormat::y420p10: planes = { Plane{ size, 2 * w, 10, 2 }, Plane{ half10, 2 * (int)half10.x, 10, 2 }, Plane{ half10, 2 * (int)half10.x, 10, 2 } }; break;
     default: throw ComputeError(CHV_ERR_BAD_INPUT, "Invalid pixel format");
     }
     for (size_t i = 0; strides && i < planes.size(); i++) {
@@ -713,6 +720,33 @@ inline ComputeContext scaleLanczosTo420(ComputeContext ctx, const std::vector<st
     return ctx;
 }
 
+// Lanczos-3 from a 10-bit decoder picture (p010 or y420p10) into an 8-bit nv12 or y420p picture (chv_scale_lanczos_hbd_to_420; DESIGN.md section
+// 4.4.10): the logical images Y, Cb and Cr resampled one by one on their 10-bit codes as scaleLanczos resamples a 1-component plane, the result
+// divided by four (exactly) before its one rounding; no dither, no colour arithmetic, no re-siting.
+inline ComputeContext scaleLanczosHbdTo420(ComputeContext ctx, const PictureSample &dst, const PictureSample &src) {
+    chv_image d, s;
+    if (!describe(dst, &d)) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    if (!describe(src, &s)) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    check(chv_scale_lanczos_hbd_to_420(ctx.get(), &d, &s));
+    return ctx;
+}
+
+// The ladder of it (chv_scale_lanczos_hbd_to_420_ladder): rungs[r][i] receives what scaleLanczosHbdTo420(ctx, rungs[r][i], srcs[i]) would write —
+// one format and one size for all sources, nv12 or y420p for all targets; one launch per route per chunk.
+inline ComputeContext scaleLanczosHbdTo420(ComputeContext ctx, const std::vector<std::vector<PictureSample>> &rungs, const std::vector<PictureSample> &srcs) {
+    const size_t n = srcs.size();
+    std::vector<chv_image> d(rungs.size() * n), s(n);
+    for (size_t i = 0; i < n; i++)
+        if (!describe(srcs[i], &s[i])) throw ComputeError(CHV_ERR_BAD_INPUT, "Bad input image");
+    for (size_t r = 0; r < rungs.size(); r++) {
+        if (rungs[r].size() != n) throw ComputeError(CHV_ERR_INVALID_VALUE, "a rung has one target per source");
+        for (size_t i = 0; i < n; i++)
+            if (!describe(rungs[r][i], &d[r * n + i])) throw ComputeError(CHV_ERR_BAD_TARGET, "target has no GPU image buffer");
+    }
+    check(chv_scale_lanczos_hbd_to_420_ladder(ctx.get(), d.data(), (int)rungs.size(), s.data(), (int)n));
+    return ctx;
+}
+
 // Many independent ticks as ONE launch (chv_batch_*): what a host with several mixers / streams on a device
 // (composer.swift:203-224) uses instead of one chv_composite per tick; byte-identical to running them one by one.
 struct Tick { PictureSample target; bool clearFirst = true; std::vector<TickLayer> layers; };
@@ -1012,6 +1046,7 @@ public:
     bool convert420 = false;          // the Lanczos scaler takes nv12 <-> y420p (off: the pair is an error, as it was)
     bool convertToRgb = false;        // the Lanczos scaler takes nv12 or y420p -> BGRA or RGBA (off: the pair is an error, as it was)
     bool convertDecoderFormats = false;      // the Lanczos scaler takes nv21, y422p, y444p, yuvs or zvuy -> nv12 or y420p (off: an error, as it was)
+    bool convertHighBitDepth = false;        // the Lanczos scaler takes p010 or y420p10 -> nv12 or y420p (off: an error, as it was)
 
     EventBox<PictureSample> operator()(const PictureSample &sample) {
         EventBox<PictureSample> r;
@@ -1030,6 +1065,9 @@ public:
                        (src.pixelFormat() == PixelFormat::nv21 || src.pixelFormat() == PixelFormat::y422p || src.pixelFormat() == PixelFormat::y444p ||
                         src.pixelFormat() == PixelFormat::yuvs || src.pixelFormat() == PixelFormat::zvuy)) {
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczosTo420(c, dst, src); });
+            } else if (scaler_ == Scaler::lanczos && convertHighBitDepth && (format_ == PixelFormat::nv12 || format_ == PixelFormat::y420p) &&
+                       (src.pixelFormat() == PixelFormat::p010 || src.pixelFormat() == PixelFormat::y420p10)) {
+                usingContext(context_, [&](ComputeContext c) { return scaleLanczosHbdTo420(c, dst, src); });
             } else if (scaler_ == Scaler::lanczos && convertToRgb && (src.pixelFormat() == PixelFormat::nv12 || src.pixelFormat() == PixelFormat::y420p) &&
                        (format_ == PixelFormat::BGRA || format_ == PixelFormat::RGBA)) {
                 usingContext(context_, [&](ComputeContext c) { return scaleLanczosFromYuv(c, dst, src, colorspace_); });
